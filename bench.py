@@ -51,9 +51,43 @@ CONFIGS = {
     "C4": (3840, 2160, "yuv444p", 8),
     "C5": (7680, 4320, "yuv444p12le", 12),
 }
-HBM_PEAK_GBS = 8000.0     # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0     # MI355X: HBM3E 8.0 TB/s spec
 PREROLL_GROUP, PREROLL_MAX = 10, 150
 EVENT_PERIOD = 4
+# --dump-outputs: values kept of the packets' bytes (float32) and of the coefficients (float64), fixed seed
+DUMP_PACKET_VALUES, DUMP_COEF_VALUES, DUMP_SEED, DUMP_MAX_BYTES = 8 << 20, 2 << 20, 20251015, 64 << 20
+
+
+def dump_outputs(out_dir, packets, status=None, coef=None):
+    """--dump-outputs: what the timed path handed its caller in its last step, as DIR/<name>.npy (float32 /
+    float64) that a run of another build with the same arguments can be compared with, file for file.
+      packet_sizes, packet_status, packet_crc32 : one value per frame (CRC-32 of the whole packet)
+      packet_bytes  : the packets' bytes, concatenated in frame order; all of them when they fit, else the
+                      bytes at DUMP_PACKET_VALUES positions drawn with DUMP_SEED (sorted)
+      coef_sample   : with a coefficient sink, the int32 coefficients at DUMP_COEF_VALUES positions of the
+                      flattened (frames, block_planes, 4096) array drawn with DUMP_SEED (sorted), exact in float64
+    Returns the result line's "outputs_dumped" block."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    arrays = {"packet_sizes": np.array([len(p) for p in packets], np.float64),
+              "packet_crc32": np.array([zlib.crc32(p) for p in packets], np.float64)}
+    if status is not None:
+        arrays["packet_status"] = np.asarray(status, np.float64)
+    stream = np.frombuffer(b"".join(packets), np.uint8)
+    if stream.size > DUMP_PACKET_VALUES:
+        stream = stream[np.sort(rng.integers(0, stream.size, DUMP_PACKET_VALUES))]
+    arrays["packet_bytes"] = stream.astype(np.float32)
+    if coef is not None:
+        flat = coef.reshape(-1)
+        n = min(DUMP_COEF_VALUES, flat.numel())
+        idx = np.sort(rng.integers(0, flat.numel(), n)) if flat.numel() > n else np.arange(n)
+        arrays["coef_sample"] = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy().astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(n + ".npy" for n in arrays), "bytes": total}
 
 
 def yuv420_of(frame):
@@ -175,6 +209,10 @@ def lanecoder_bench(args, enc0, FFV2Encoder, synth, cfg, dist_cfg, barrier):
         buf, offs, sizes, status = finish()
     barrier()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, [buf[int(offs[f]): int(offs[f]) + int(sizes[f])].tobytes() for f in range(F)],
+                              status)
     if world > 1:
         import torch.distributed as dist
         tt = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
@@ -262,6 +300,8 @@ def lanecoder_bench(args, enc0, FFV2Encoder, synth, cfg, dist_cfg, barrier):
                                    "gpu_packets_match_cpu": bool(ok)}
             if not ok:
                 res["error"] = "GPU packets differ from the CPU oracle"
+        if dumped is not None:
+            res["outputs_dumped"] = dumped
         print(json.dumps(res))
     enc.close()
     if world > 1:
@@ -401,12 +441,17 @@ def main():
                     help="with --frames-in-flight: bytes of HBM reserved per packet (0 = the encoder's bound for any qp)")
     ap.add_argument("--qp", type=int, default=0,
                     help="informational: qp > 0 times ffv2amd_encode_batch_to_host (GPU transform + PVQ, host range coder)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (packets; coefficients when they are "
+                         "materialised) as DIR/<name>.npy, float32/float64, at most 64 MB: rank 0's frames")
     args = ap.parse_args()
     lane_mode = args.qp > 0 and not args.host_coder and not args.device_coder
     if args.steps is None:
         args.steps = 10 if lane_mode else 200
     if args.warmup is None:
         args.warmup = 1 if lane_mode else 50
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # before the HIP runtime initialises (and inherited by the ranks started below): see ffmpeg_ffv2_amd/_lib.py
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
@@ -497,6 +542,7 @@ def main():
             pk = enc.qp_finish()                          # ... behind the host half of step i
         barrier()
         dt = time.perf_counter() - t0
+        dumped = dump_outputs(args.dump_outputs, pk) if args.dump_outputs and rank == 0 else None
         if world > 1:
             tt = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -528,6 +574,8 @@ def main():
                                        "gpu_packets_match_cpu": bool(ok)}
                 if not ok:
                     res["error"] = "GPU packets differ from the CPU oracle"
+            if dumped is not None:
+                res["outputs_dumped"] = dumped
             print(json.dumps(res))
         enc.close()
         if world > 1:
@@ -572,6 +620,12 @@ def main():
     elapsed = t1 - t0
     t_ms, e_ms, launches, t_lo, t_hi = enc.profile_read_ex()
     enc.profile(False)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before the steady-state loops below write the same buffers again
+        last = outs[(args.steps - 1) & 1]
+        dumped = dump_outputs(args.dump_outputs, enc.collect(*last), last[2].cpu().numpy(),
+                              None if args.no_coef else coef)
 
     # ---- steady state, untimed (not part of `value`): the same launch back to back for
     # --steady-seconds, first with timing events around every kernel (mean / min / max of the
@@ -742,6 +796,8 @@ def main():
                          "launches_timed": launches,
                          "timed_every_nth_step": period},
         }
+        if dumped is not None:
+            result["outputs_dumped"] = dumped
         if steady is not None:
             result["steady_state"] = steady
             if steady["launches_timed"]:
