@@ -10,9 +10,10 @@
  *            at QP 0 (the asynchronous ring), batches of N frames coded side by side on the device at QP > 0
  *            (FFV2AMDCodecContext.qp_frames_per_call; drained with send_frame(NULL) at the end of the input).
  *   PIX_FMT: gray | yuv444p | yuv444p10le | yuv444p12le | gbrp | gbrp10le | gbrp12le
- *            yuv420p | yuv420p10le | yuv420p12le are converted first, as the ffmpeg tool does
- *            (choose_pixel_fmt -> yuv444p* + auto-inserted bicubic scale filter); --no-convert
- *            as a last argument hands them to encode2 unconverted, which refuses them (exit 2).
+ *            yuv420p | yuv420p10le | yuv420p12le and yuv422p | yuv422p10le | yuv422p12le are converted
+ *            first, as the ffmpeg tool does (choose_pixel_fmt -> yuv444p* + auto-inserted bicubic scale
+ *            filter); --no-convert as a last argument hands them to encode2 unconverted, which refuses
+ *            them (exit 2).
  * An output name ending in ".mkv" selects the Matroska writer (include/ffv2_amd_mkv.h,
  * "V_FFV2", 25 frames per second) instead of the back-to-back packet stream.
  */
@@ -24,15 +25,18 @@
 #include "ffv2_amd_codec.h"
 #include "ffv2_amd_mkv.h"
 
-static int parse_fmt(const char *s, int *planes, int *bps, int *is420)
+/* *sub: 0 for an encoder format, 420 / 422 for a subsampled source converted to the yuv444p* format returned */
+static int parse_fmt(const char *s, int *planes, int *bps, int *sub)
 {
-    static const struct { const char *n; int id, bps; } sub[] = {
-        { "yuv420p", FFV2AMD_PIX_YUV444P, 1 }, { "yuv420p10le", FFV2AMD_PIX_YUV444P10LE, 2 },
-        { "yuv420p12le", FFV2AMD_PIX_YUV444P12LE, 2 },
+    static const struct { const char *n; int id, bps, sub; } conv[] = {
+        { "yuv420p", FFV2AMD_PIX_YUV444P, 1, 420 }, { "yuv420p10le", FFV2AMD_PIX_YUV444P10LE, 2, 420 },
+        { "yuv420p12le", FFV2AMD_PIX_YUV444P12LE, 2, 420 },
+        { "yuv422p", FFV2AMD_PIX_YUV444P, 1, 422 }, { "yuv422p10le", FFV2AMD_PIX_YUV444P10LE, 2, 422 },
+        { "yuv422p12le", FFV2AMD_PIX_YUV444P12LE, 2, 422 },
     };
-    *is420 = 0;
-    for (size_t i = 0; i < sizeof(sub) / sizeof(sub[0]); i++)
-        if (!strcmp(s, sub[i].n)) { *planes = 3; *bps = sub[i].bps; *is420 = 1; return sub[i].id; }
+    *sub = 0;
+    for (size_t i = 0; i < sizeof(conv) / sizeof(conv[0]); i++)
+        if (!strcmp(s, conv[i].n)) { *planes = 3; *bps = conv[i].bps; *sub = conv[i].sub; return conv[i].id; }
     static const struct { const char *n; int id, planes, bps; } tab[] = {
         { "gray", FFV2AMD_PIX_GRAY8, 1, 1 },           { "yuv444p", FFV2AMD_PIX_YUV444P, 3, 1 },
         { "gbrp", FFV2AMD_PIX_GBRP, 3, 1 },            { "yuv444p10le", FFV2AMD_PIX_YUV444P10LE, 3, 2 },
@@ -50,12 +54,12 @@ int main(int argc, char **argv)
         fprintf(stderr, "usage: %s WIDTH HEIGHT PIX_FMT IN.yuv OUT.ffv2 [QP] [HIP_DEVICE] [--async N]\n", argv[0]);
         return 2;
     }
-    int planes = 0, bps = 0, is420 = 0;
+    int planes = 0, bps = 0, sub = 0;
     FFV2AMDCodecContext ctx = { 0 };
     ctx.width = atoi(argv[1]);
     ctx.height = atoi(argv[2]);
-    ctx.pix_fmt = parse_fmt(argv[3], &planes, &bps, &is420);
-    if (is420 && !strcmp(argv[argc - 1], "--no-convert")) {
+    ctx.pix_fmt = parse_fmt(argv[3], &planes, &bps, &sub);
+    if (sub && !strcmp(argv[argc - 1], "--no-convert")) {
         fprintf(stderr, "%s is not an encoder input (ffv2enc.c:596-601)\n", argv[3]);
         return 2;
     }
@@ -77,9 +81,10 @@ int main(int argc, char **argv)
     if (ret < 0) { fprintf(stderr, "init failed: %d\n", ret); return 1; }
 
     const size_t plane_bytes = (size_t)ctx.width * ctx.height * bps;
-    const int cw = (ctx.width + 1) / 2, ch = (ctx.height + 1) / 2;
+    const int cw = (ctx.width + 1) / 2, ch = sub == 422 ? ctx.height : (ctx.height + 1) / 2;
     const size_t cplane_bytes = (size_t)cw * ch * bps;
-    const size_t frame_bytes = is420 ? plane_bytes + 2 * cplane_bytes : plane_bytes * planes;
+    const size_t frame_bytes = sub ? plane_bytes + 2 * cplane_bytes : plane_bytes * planes;
+    const unsigned sub_flag = sub == 420 ? FFV2AMD_FRAME_YUV420 : sub == 422 ? FFV2AMD_FRAME_YUV422 : 0;
     uint8_t *buf = malloc(frame_bytes);
     if (!buf) return 1;
     long nframes = 0;
@@ -97,13 +102,13 @@ int main(int argc, char **argv)
             FFV2AMDFrame fr = { 0 };
             if (!have) eof = 1;
             for (int p = 0; p < planes && have; p++) {
-                fr.data[p] = is420 ? (p ? buf + plane_bytes + (p - 1) * cplane_bytes : buf) : buf + p * plane_bytes;
-                fr.linesize[p] = (ptrdiff_t)(is420 && p ? cw : ctx.width) * bps;
+                fr.data[p] = sub ? (p ? buf + plane_bytes + (p - 1) * cplane_bytes : buf) : buf + p * plane_bytes;
+                fr.linesize[p] = (ptrdiff_t)(sub && p ? cw : ctx.width) * bps;
             }
             fr.pts = sent;
             for (;;) {
                 if (have) {
-                    ret = ffv2amd_codec_send_frame(&ctx, &fr, is420 ? FFV2AMD_FRAME_YUV420 : 0);
+                    ret = ffv2amd_codec_send_frame(&ctx, &fr, sub_flag);
                     if (ret == 0) { sent++; break; }                    /* next frame */
                     if (ret != FFV2AMD_ERR_AGAIN) { done = 1; break; }
                 } else if (!drained) {
@@ -131,11 +136,13 @@ int main(int argc, char **argv)
         FFV2AMDPacket pkt = { 0 };
         int got = 0;
         for (int p = 0; p < planes; p++) {
-            fr.data[p] = is420 ? (p ? buf + plane_bytes + (p - 1) * cplane_bytes : buf) : buf + p * plane_bytes;
-            fr.linesize[p] = (ptrdiff_t)(is420 && p ? cw : ctx.width) * bps;
+            fr.data[p] = sub ? (p ? buf + plane_bytes + (p - 1) * cplane_bytes : buf) : buf + p * plane_bytes;
+            fr.linesize[p] = (ptrdiff_t)(sub && p ? cw : ctx.width) * bps;
         }
         fr.pts = nframes;
-        ret = is420 ? ffv2amd_codec_encode_yuv420(&ctx, &pkt, &fr, &got) : ffv2amd_codec_encode2(&ctx, &pkt, &fr, &got);
+        ret = sub == 420 ? ffv2amd_codec_encode_yuv420(&ctx, &pkt, &fr, &got)
+            : sub == 422 ? ffv2amd_codec_encode_yuv422(&ctx, &pkt, &fr, &got)
+            : ffv2amd_codec_encode2(&ctx, &pkt, &fr, &got);
         if (ret < 0 || !got) { fprintf(stderr, "encode2 failed on frame %ld: %d\n", nframes, ret); break; }
         if (mkv) ret = ffv2amd_mkv_write_packet(mkv, pkt.data, (size_t)pkt.size, pkt.pts);
         else     fwrite(pkt.data, 1, (size_t)pkt.size, out);

@@ -386,6 +386,9 @@ void run_parallel(int n, int want, Fn fn)
     for (auto &t : pool) t.join();
 }
 
+// What a frame's chroma is when it reaches the device: ready (4:4:4), or waiting for the up-conversion
+enum ChromaKind : uint8_t { CHROMA_444 = 0, CHROMA_420 = 1, CHROMA_422 = 2 };
+
 // A few persistent host threads that gather the rows of a caller's (pageable) frame into pinned
 // memory, slice by slice, each slice's DMA issued by the thread that gathered it.  The calling
 // thread takes part; with no workers (thread creation failed) it does everything itself.
@@ -658,6 +661,7 @@ struct ffv2amd_encoder {
     uint8_t *qh_frame[2] = { nullptr, nullptr }, *qd_frame[2] = { nullptr, nullptr };
     int32_t *qd_w[2] = { nullptr, nullptr };
     uint8_t *qd_c420[2] = { nullptr, nullptr };          // U, V of a 4:2:0 frame (ffv2amd_qp_send_frame_420)
+    uint8_t *qd_c422[2] = { nullptr, nullptr };          // U, V of a 4:2:2 frame (ffv2amd_qp_send_frame_422)
     int64_t q_tag[2] = { 0, 0 };
     // decoder-side check (ffv2amd_decode_frame)
     int16_t *d_dec_pulses = nullptr;
@@ -671,6 +675,10 @@ struct ffv2amd_encoder {
     FFV2Upconv *upconv = nullptr;
     bool upconv_tried = false;
     uint8_t *d_420 = nullptr, *h_420 = nullptr;
+    // 4:2:2 -> 4:4:4 front end (ffv2amd_*_422)
+    FFV2Upconv422 *upconv422 = nullptr;
+    bool upconv422_tried = false;
+    uint8_t *d_422 = nullptr, *h_422 = nullptr;
     // asynchronous frame ring (ffv2amd_ring_*)
     struct RingSlot {
         uint8_t  *h_frame = nullptr, *d_frame = nullptr;    // pinned staging frame, device frame
@@ -680,6 +688,7 @@ struct ffv2amd_encoder {
         int32_t  *d_w = nullptr;
         bool has_w = false;
         uint8_t  *d_c420 = nullptr;                         // U, V of a 4:2:0 frame, rows c_pitch apart (ring_send_420)
+        uint8_t  *d_c422 = nullptr;                         // U, V of a 4:2:2 frame, h rows each (ring_send_422)
         hipEvent_t ev_h2d = nullptr, ev_done = nullptr, ev_meta = nullptr;
         int64_t tag = 0;
     };
@@ -748,10 +757,12 @@ struct ffv2amd_encoder {
         int calls = 2;                           // lane coder calls in flight
         uint8_t *d_frames[NBUF] = {};
         uint8_t *d_c420[NBUF] = {};              // 4:2:0 chroma as it arrives: [cap][U plane, V plane]
+        uint8_t *d_c422[NBUF] = {};              // 4:2:2 chroma as it arrives: [cap][U plane, V plane]
         int32_t *d_w[NBUF] = {};
         bool any_w[NBUF] = {};
         std::vector<int64_t> tags[NBUF];
-        std::vector<uint8_t> is420[NBUF];        // per frame of the batch: its chroma waits in d_c420 for the up-conversion
+        std::vector<uint8_t> chroma[NBUF];       // per frame of the batch, a ChromaKind: 4:2:0 / 4:2:2 chroma waits in
+                                                 // d_c420 / d_c422 for the up-conversion
         int fill = 0, count = 0;                 // buffer being filled, frames in it
         int flight[4] = { -1, -1, -1, -1 };      // buffers of the calls in flight, oldest first
         int flight_n[4] = { 0, 0, 0, 0 };
@@ -866,6 +877,9 @@ void ffv2amd_encoder_destroy(ffv2amd_encoder *e)
     ffv2_upconv_destroy(e->upconv);
     (void)hipFree(e->d_420);
     if (e->h_420) (void)hipHostFree(e->h_420);
+    ffv2_upconv422_destroy(e->upconv422);
+    (void)hipFree(e->d_422);
+    if (e->h_422) (void)hipHostFree(e->h_422);
     lanecoder_free(e);
     for (auto &q : e->qset) {
         (void)hipFree(q.d_rec); (void)hipFree(q.d_stream); (void)hipFree(q.d_totals); (void)hipFree(q.d_codes); (void)hipFree(q.d_status);
@@ -882,7 +896,7 @@ void ffv2amd_encoder_destroy(ffv2amd_encoder *e)
     }
     if (e->q_copy) { (void)hipStreamSynchronize(e->q_copy); (void)hipStreamDestroy(e->q_copy); }
     for (int k = 0; k < 2; k++) {
-        (void)hipFree(e->qd_frame[k]); (void)hipFree(e->qd_w[k]); (void)hipFree(e->qd_c420[k]);
+        (void)hipFree(e->qd_frame[k]); (void)hipFree(e->qd_w[k]); (void)hipFree(e->qd_c420[k]); (void)hipFree(e->qd_c422[k]);
         if (e->qh_frame[k]) (void)hipHostFree(e->qh_frame[k]);
     }
     (void)hipFree(e->d_thr); (void)hipFree(e->d_lds_scan); (void)hipFree(e->d_prefix);
@@ -1381,6 +1395,99 @@ int ffv2amd_encode_frame_420(ffv2amd_encoder *e, const uint8_t *const data[3], c
     hipStream_t s = e->stream;
     HIPCHK(hipMemcpyAsync(e->d_420, e->h_420, total, hipMemcpyHostToDevice, s));
     HIPCHK(ffv2_launch_upconv(e->upconv, e->geom, 1, e->d_420, total, e->d_frame, s));
+    return encode_uploaded_frame(e, qp, nullptr, out, out_cap, out_size);
+}
+
+// ------------------------------------------------------------------
+// 4:2:2 front end: the same tool chain step for yuv422p / yuv422p10le / yuv422p12le (the format
+// choice of libavutil/pixdesc.c:2838-2873, then libswscale's generic scaler: chroma 2x up along x,
+// unscaled along y) -- see ffv2_upconv.hip.  Same encoder rule as 4:2:0.  PARITY UNPINNED.
+// ------------------------------------------------------------------
+static int upconv422_ready(ffv2amd_encoder *e)
+{
+    const ffv2amd_info &in = e->info;
+    if (in.planes != 3 || (in.pix_fmt != FFV2AMD_PIX_YUV444P && in.pix_fmt != FFV2AMD_PIX_YUV444P10LE &&
+                           in.pix_fmt != FFV2AMD_PIX_YUV444P12LE))
+        return FFV2AMD_ERR_INVAL;
+    if (!e->upconv422 && !e->upconv422_tried) {
+        e->upconv422_tried = true;
+        e->upconv422 = ffv2_upconv422_create(in.width, in.depth, e->stream);   // table upload on the encoder's stream, waited for
+    }
+    return e->upconv422 ? FFV2AMD_OK : FFV2AMD_ERR_UNSUPPORTED;
+}
+
+size_t ffv2amd_frame_bytes_422(const ffv2amd_encoder *e)
+{
+    return e ? ffv2_upconv422_src_frame_bytes(e->info.width, e->info.height, e->info.depth) : 0;
+}
+
+int ffv2amd_upconvert_422_device(ffv2amd_encoder *e, int nframes, const void *d_src422, void *d_frames444, void *stream)
+{
+    if (!e || !d_src422 || !d_frames444 || nframes < 1) return FFV2AMD_ERR_INVAL;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return FFV2AMD_ERR_DEVICE;
+    int r = upconv422_ready(e);
+    if (r < 0) return r;
+    HIPCHK(ffv2_launch_upconv422(e->upconv422, e->geom, nframes, (const uint8_t *)d_src422, ffv2amd_frame_bytes_422(e),
+                                 (uint8_t *)d_frames444, (hipStream_t)stream));
+    return FFV2AMD_OK;
+}
+
+int ffv2amd_debug_upconv422_time(ffv2amd_encoder *e, int nframes, const void *d_src422, void *d_frames444, int reps,
+                                 float *ms_per_launch)
+{
+    if (!e || !d_src422 || !d_frames444 || !ms_per_launch || nframes < 1 || reps < 1) return FFV2AMD_ERR_INVAL;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return FFV2AMD_ERR_DEVICE;
+    int r = upconv422_ready(e);
+    if (r < 0) return r;
+    const ffv2amd_info &in = e->info;
+    const size_t bps = in.depth > 8 ? 2 : 1, cw = (size_t)((in.width + 1) >> 1), total = ffv2amd_frame_bytes_422(e);
+    const uint8_t *src_u = (const uint8_t *)d_src422 + (size_t)in.width * in.height * bps;
+    hipStream_t s = e->stream;
+    auto launch = [&]() {
+        return ffv2_launch_upconv422_chroma(e->upconv422, e->geom, nframes, src_u, cw * bps, cw * in.height * bps, total,
+                                            (uint8_t *)d_frames444, s);
+    };
+    hipEvent_t a, b;
+    HIPCHK(hipEventCreate(&a));
+    HIPCHK(hipEventCreate(&b));
+    HIPCHK(launch());                                              // warm
+    HIPCHK(hipEventRecord(a, s));
+    for (int i = 0; i < reps; i++) HIPCHK(launch());
+    HIPCHK(hipEventRecord(b, s));
+    HIPCHK(hipEventSynchronize(b));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, a, b));
+    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+    *ms_per_launch = ms / reps;
+    return FFV2AMD_OK;
+}
+
+int ffv2amd_encode_frame_422(ffv2amd_encoder *e, const uint8_t *const data[3], const ptrdiff_t linesize[3],
+                             int qp, uint8_t *out, size_t out_cap, size_t *out_size)
+{
+    if (!e || !data || !linesize || !out || !out_size || !data[0] || !data[1] || !data[2]) return FFV2AMD_ERR_INVAL;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return FFV2AMD_ERR_DEVICE;
+    int r = upconv422_ready(e);
+    if (r < 0) return r;
+    const ffv2amd_info &in = e->info;
+    const size_t bps = in.depth > 8 ? 2 : 1, total = ffv2amd_frame_bytes_422(e);
+    if (!e->d_422) {
+        HIPCHK(hipMalloc(&e->d_422, total));
+        HIPCHK(hipHostMalloc(&e->h_422, total, hipHostMallocDefault));
+    }
+    const int cw = (in.width + 1) >> 1;
+    uint8_t *dst = e->h_422;
+    for (int p = 0; p < 3; p++) {                                  // tight rows: Y, U, V
+        const int w = p ? cw : in.width;
+        for (int y = 0; y < in.height; y++, dst += (size_t)w * bps)
+            memcpy(dst, data[p] + (ptrdiff_t)y * linesize[p], (size_t)w * bps);
+    }
+    hipStream_t s = e->stream;
+    HIPCHK(hipMemcpyAsync(e->d_422, e->h_422, total, hipMemcpyHostToDevice, s));
+    HIPCHK(ffv2_launch_upconv422(e->upconv422, e->geom, 1, e->d_422, total, e->d_frame, s));
     return encode_uploaded_frame(e, qp, nullptr, out, out_cap, out_size);
 }
 
@@ -2289,6 +2396,46 @@ int ffv2amd_qp_send_frame_420(ffv2amd_encoder *e, const uint8_t *const data[3], 
     return FFV2AMD_OK;
 }
 
+// ... and for a yuv422p* frame: chroma h rows high, up-converted along x only (ffv2_upconv.hip)
+int ffv2amd_qp_send_frame_422(ffv2amd_encoder *e, const uint8_t *const data[3], const ptrdiff_t linesize[3], int qp, int64_t tag)
+{
+    if (!e || !data || !linesize || !data[0] || !data[1] || !data[2]) return FFV2AMD_ERR_INVAL;
+    if (qp < 1 || qp > 64) return FFV2AMD_ERR_UNSUPPORTED;
+    if (e->q_sub - e->q_fin >= 2) return FFV2AMD_ERR_AGAIN;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return FFV2AMD_ERR_DEVICE;
+    int r = upconv422_ready(e);
+    if (r < 0) return r;
+    const ffv2amd_info &in = e->info;
+    const int k = (int)(e->q_sub & 1u);
+    const size_t bps = in.depth > 8 ? 2 : 1;
+    const int cw = (in.width + 1) >> 1, ch = in.height;
+    const size_t c_pitch = align_up((size_t)cw * bps, 128);
+    if (!e->qd_frame[k]) {
+        HIPCHK(hipMalloc(&e->qd_frame[k], in.frame_stride));
+        HIPCHK(hipMalloc(&e->qd_w[k], sizeof(int32_t) * in.block_planes));
+        HIPCHK(hipHostMalloc(&e->qh_frame[k], in.frame_stride, hipHostMallocDefault));
+        memset(e->qh_frame[k], 0, in.frame_stride);
+    }
+    if (!e->qd_c422[k]) HIPCHK(hipMalloc(&e->qd_c422[k], 2 * c_pitch * (size_t)ch));
+    // staging: luma in plane 0 of the page-locked frame, U and V behind it (2 * h * c_pitch <= 2 * h * row_pitch:
+    // they fit planes 1 and 2)
+    uint8_t *hy = e->qh_frame[k], *hc = e->qh_frame[k] + in.plane_stride;
+    for (int y = 0; y < in.height; y++)
+        memcpy(hy + (size_t)y * in.row_pitch, data[0] + (ptrdiff_t)y * linesize[0], (size_t)in.width * bps);
+    for (int p = 0; p < 2; p++)
+        for (int y = 0; y < ch; y++)
+            memcpy(hc + ((size_t)p * ch + y) * c_pitch, data[1 + p] + (ptrdiff_t)y * linesize[1 + p], (size_t)cw * bps);
+    hipStream_t s = e->stream;
+    HIPCHK(hipMemcpyAsync(e->qd_frame[k], hy, in.row_pitch * (size_t)in.height, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(e->qd_c422[k], hc, 2 * c_pitch * (size_t)ch, hipMemcpyHostToDevice, s));
+    HIPCHK(ffv2_launch_upconv422_chroma(e->upconv422, e->geom, 1, e->qd_c422[k], c_pitch, c_pitch * (size_t)ch, 0, e->qd_frame[k], s));
+    r = ffv2amd_qp_submit(e, 1, e->qd_frame[k], qp, nullptr);
+    if (r < 0) return r;
+    e->q_tag[k] = tag;
+    return FFV2AMD_OK;
+}
+
 int ffv2amd_qp_receive_packet(ffv2amd_encoder *e, uint8_t *out, size_t out_cap, size_t *out_size, int64_t *tag)
 {
     if (!e || !out || !out_size) return FFV2AMD_ERR_INVAL;
@@ -2325,8 +2472,8 @@ int ffv2amd_qpring_close(ffv2amd_encoder *e)
     (void)hipStreamSynchronize(e->stream);
     (void)ffv2amd_lanecoder_close(e);
     for (int i = 0; i < ffv2amd_encoder::QpRing::NBUF; i++) {
-        (void)hipFree(r.d_frames[i]); (void)hipFree(r.d_c420[i]); (void)hipFree(r.d_w[i]);
-        r.d_frames[i] = nullptr; r.d_c420[i] = nullptr; r.d_w[i] = nullptr; r.any_w[i] = false; r.tags[i].clear();
+        (void)hipFree(r.d_frames[i]); (void)hipFree(r.d_c420[i]); (void)hipFree(r.d_c422[i]); (void)hipFree(r.d_w[i]);
+        r.d_frames[i] = nullptr; r.d_c420[i] = nullptr; r.d_c422[i] = nullptr; r.d_w[i] = nullptr; r.any_w[i] = false; r.tags[i].clear();
     }
     for (int i = 0; i < ffv2amd_encoder::QpRing::NBOUNCE; i++) {
         if (r.bounce[i]) (void)hipHostFree(r.bounce[i]);
@@ -2405,7 +2552,7 @@ static int qpring_open_with(ffv2amd_encoder *e, int qp, int frames_per_call, siz
     QK(hipEventCreateWithFlags(&r.ev_batch, hipEventDisableTiming));
     for (int i = 0; i <= calls; i++) {
         QK(hipMalloc(&r.d_frames[i], in.frame_stride * (size_t)frames_per_call));
-        try { r.tags[i].assign((size_t)frames_per_call, 0); r.is420[i].assign((size_t)frames_per_call, 0); }
+        try { r.tags[i].assign((size_t)frames_per_call, 0); r.chroma[i].assign((size_t)frames_per_call, CHROMA_444); }
         catch (...) { r.open = true; ffv2amd_qpring_close(e); return FFV2AMD_ERR_NOMEM; }
     }
     r.h_cap = (size_t)frames_per_call * (r.pcap + 16);
@@ -2464,18 +2611,25 @@ static int qpring_submit(ffv2amd_encoder *e)
     HIPCHK(hipEventRecord(r.ev_batch, r.h2d));
     HIPCHK(hipStreamWaitEvent(e->stream, r.ev_batch, 0));
     const int b = r.fill;
-    {   // 4:2:0 frames of the batch: their chroma is up-converted now, one launch per run of such frames (a launch per
-        // frame on the copy stream stood in the queue behind the coder's long kernels every other run)
+    {   // 4:2:0 and 4:2:2 frames of the batch: their chroma is up-converted now, one launch per run of frames of one
+        // kind (a launch per frame on the copy stream stood in the queue behind the coder's long kernels every other run)
         const ffv2amd_info &in = e->info;
         const size_t bps = in.depth > 8 ? 2 : 1;
         const int cw = (in.width + 1) >> 1, ch = (in.height + 1) >> 1;
         const size_t c_pitch = align_up((size_t)cw * bps, 128), c_frame = 2 * c_pitch * (size_t)ch;
+        const size_t c_frame422 = 2 * c_pitch * (size_t)in.height;
         for (int i0 = 0; i0 < r.count; ) {
-            if (!r.is420[b][(size_t)i0]) { i0++; continue; }
+            const uint8_t kind = r.chroma[b][(size_t)i0];
+            if (kind == CHROMA_444) { i0++; continue; }
             int i1 = i0;
-            while (i1 < r.count && r.is420[b][(size_t)i1]) i1++;
-            HIPCHK(ffv2_launch_upconv_chroma(e->upconv, e->geom, i1 - i0, r.d_c420[b] + (size_t)i0 * c_frame, c_pitch,
-                                             c_pitch * (size_t)ch, c_frame, r.d_frames[b] + (size_t)i0 * in.frame_stride, e->stream));
+            while (i1 < r.count && r.chroma[b][(size_t)i1] == kind) i1++;
+            if (kind == CHROMA_420)
+                HIPCHK(ffv2_launch_upconv_chroma(e->upconv, e->geom, i1 - i0, r.d_c420[b] + (size_t)i0 * c_frame, c_pitch,
+                                                 c_pitch * (size_t)ch, c_frame, r.d_frames[b] + (size_t)i0 * in.frame_stride, e->stream));
+            else
+                HIPCHK(ffv2_launch_upconv422_chroma(e->upconv422, e->geom, i1 - i0, r.d_c422[b] + (size_t)i0 * c_frame422, c_pitch,
+                                                    c_pitch * (size_t)in.height, c_frame422,
+                                                    r.d_frames[b] + (size_t)i0 * in.frame_stride, e->stream));
             i0 = i1;
         }
     }
@@ -2500,9 +2654,11 @@ int ffv2amd_qpring_send(ffv2amd_encoder *e, const uint8_t *const data[4], const 
     auto &r = e->qr;
     if (!r.open) return FFV2AMD_ERR_INVAL;
     const ffv2amd_info &in = e->info;
-    const bool is420 = (flags & FFV2AMD_FRAME_YUV420) != 0;
-    const int npl = is420 ? 3 : in.planes;
-    if (is420 && in.planes != 3) return FFV2AMD_ERR_INVAL;
+    const bool is420 = (flags & FFV2AMD_FRAME_YUV420) != 0, is422 = (flags & FFV2AMD_FRAME_YUV422) != 0;
+    if (is420 && is422) return FFV2AMD_ERR_INVAL;
+    const bool sub = is420 || is422;                             // chroma goes to staging, luma into plane 0
+    const int npl = sub ? 3 : in.planes;
+    if (sub && in.planes != 3) return FFV2AMD_ERR_INVAL;
     for (int p = 0; p < npl; p++)
         if (!data[p]) return FFV2AMD_ERR_INVAL;
     DeviceGuard guard(e->device);
@@ -2513,24 +2669,29 @@ int ffv2amd_qpring_send(ffv2amd_encoder *e, const uint8_t *const data[4], const 
     }
     const int b = r.fill;
     const size_t bps = in.depth > 8 ? 2 : 1, nb = (size_t)in.block_planes;
-    const int cw = (in.width + 1) >> 1, ch = (in.height + 1) >> 1;
+    const int cw = (in.width + 1) >> 1, ch = is422 ? in.height : (in.height + 1) >> 1;
     const size_t c_pitch = align_up((size_t)cw * bps, 128);
     if (is420) {
         int rc = upconv_ready(e);
         if (rc < 0) return rc;
         if (!r.d_c420[b]) HIPCHK(hipMalloc(&r.d_c420[b], 2 * c_pitch * (size_t)ch * (size_t)r.cap));
     }
+    if (is422) {
+        int rc = upconv422_ready(e);
+        if (rc < 0) return rc;
+        if (!r.d_c422[b]) HIPCHK(hipMalloc(&r.d_c422[b], 2 * c_pitch * (size_t)ch * (size_t)r.cap));
+    }
     uint8_t *d_frame = r.d_frames[b] + (size_t)r.count * in.frame_stride;
-    uint8_t *d_c = is420 ? r.d_c420[b] + (size_t)r.count * 2 * c_pitch * (size_t)ch : nullptr;
+    uint8_t *d_c = sub ? (is422 ? r.d_c422[b] : r.d_c420[b]) + (size_t)r.count * 2 * c_pitch * (size_t)ch : nullptr;
     // where each plane goes: rows `pitch` apart on the device
     struct Pl { const uint8_t *src; ptrdiff_t ls; size_t row_bytes, pitch; int rows; uint8_t *dst; } pl[4];
     for (int p = 0; p < npl; p++) {
-        const bool chroma = is420 && p > 0;
+        const bool chroma = sub && p > 0;
         pl[p].src = data[p]; pl[p].ls = linesize[p];
         pl[p].row_bytes = (size_t)(chroma ? cw : in.width) * bps;
         pl[p].pitch = chroma ? c_pitch : in.row_pitch;
         pl[p].rows = chroma ? ch : in.height;
-        pl[p].dst = chroma ? d_c + (size_t)(p - 1) * c_pitch * (size_t)ch : d_frame + (size_t)(is420 ? 0 : p) * in.plane_stride;
+        pl[p].dst = chroma ? d_c + (size_t)(p - 1) * c_pitch * (size_t)ch : d_frame + (size_t)(sub ? 0 : p) * in.plane_stride;
     }
     hipStream_t sh = r.h2d;
     bool in_place = (flags & FFV2AMD_FRAME_PINNED) != 0;
@@ -2591,7 +2752,7 @@ int ffv2amd_qpring_send(ffv2amd_encoder *e, const uint8_t *const data[4], const 
         }
         HIPCHK(hipEventRecord(r.ev_bounce[k], sh));
     }
-    r.is420[b][(size_t)r.count] = is420 ? 1 : 0;                 // up-converted when the batch leaves (qpring_submit)
+    r.chroma[b][(size_t)r.count] = is420 ? CHROMA_420 : is422 ? CHROMA_422 : CHROMA_444;   // up-converted when the batch leaves (qpring_submit)
     if (W) {
         if (!r.d_w[b]) HIPCHK(hipMalloc(&r.d_w[b], sizeof(int32_t) * nb * (size_t)r.cap));
         if (!r.any_w[b]) {
@@ -2776,7 +2937,7 @@ void ffv2amd_ring_close(ffv2amd_encoder *e)
         if (st) (void)hipStreamSynchronize(st);
     for (auto &r : e->ring) {
         (void)hipFree(r.d_frame); (void)hipFree(r.d_pkt); (void)hipFree(r.d_meta);
-        (void)hipFree(r.d_codes); (void)hipFree(r.d_bitcnt); (void)hipFree(r.d_w); (void)hipFree(r.d_c420);
+        (void)hipFree(r.d_codes); (void)hipFree(r.d_bitcnt); (void)hipFree(r.d_w); (void)hipFree(r.d_c420); (void)hipFree(r.d_c422);
         if (r.h_frame) (void)hipHostFree(r.h_frame);
         if (r.h_pkt) (void)hipHostFree(r.h_pkt);
         if (r.h_meta) (void)hipHostFree(r.h_meta);
@@ -2874,9 +3035,9 @@ struct RingPlane {
     uint8_t *d_dst, *stage;
 };
 
-// H2D of the planes, then T-stage + E-stage on a compute stream (4:2:0: the chroma up-conversion in
-// front of them), then the {size, status} D2H: the body of ring_send / ring_send_420.
-static int ring_submit(ffv2amd_encoder *e, ffv2amd_encoder::RingSlot &r, const RingPlane *pl, int npl, bool chroma420,
+// H2D of the planes, then T-stage + E-stage on a compute stream (4:2:0, 4:2:2: the chroma up-conversion in
+// front of them), then the {size, status} D2H: the body of ring_send / ring_send_420 / ring_send_422.
+static int ring_submit(ffv2amd_encoder *e, ffv2amd_encoder::RingSlot &r, const RingPlane *pl, int npl, ChromaKind chroma,
                        const int32_t *W, int64_t tag, unsigned flags)
 {
     const ffv2amd_info &in = e->info;
@@ -2951,9 +3112,12 @@ static int ring_submit(ffv2amd_encoder *e, ffv2amd_encoder::RingSlot &r, const R
     HIPCHK(hipEventRecord(r.ev_h2d, sh));
     hipStream_t sc = e->ring_comp[e->ring_seq++ & 1u];
     HIPCHK(hipStreamWaitEvent(sc, r.ev_h2d, 0));
-    if (chroma420)
+    if (chroma == CHROMA_420)
         HIPCHK(ffv2_launch_upconv_chroma(e->upconv, e->geom, 1, r.d_c420, pl[1].pitch, pl[1].pitch * (size_t)pl[1].rows, 0,
                                          r.d_frame, sc));
+    else if (chroma == CHROMA_422)
+        HIPCHK(ffv2_launch_upconv422_chroma(e->upconv422, e->geom, 1, r.d_c422, pl[1].pitch, pl[1].pitch * (size_t)pl[1].rows, 0,
+                                            r.d_frame, sc));
     int rc = launch_encode_qp0(e, 1, r.d_frame, dW, r.d_pkt, in.packet_cap, r.d_meta, (int32_t *)(r.d_meta + 1),
                                r.d_codes, r.d_bitcnt, nullptr, sc, sc, nullptr, (int32_t *)(r.d_meta + 2));
     if (rc < 0) return rc;
@@ -2981,7 +3145,7 @@ int ffv2amd_ring_send(ffv2amd_encoder *e, const uint8_t *const data[4], const pt
     for (int p = 0; p < in.planes; p++)
         pl[p] = RingPlane{ data[p], linesize[p], (size_t)in.width * (in.depth > 8 ? 2 : 1), in.row_pitch, in.height, 4,
                            r.d_frame + (size_t)p * in.plane_stride, r.h_frame + (size_t)p * in.plane_stride };
-    return ring_submit(e, r, pl, in.planes, false, W, tag, flags);
+    return ring_submit(e, r, pl, in.planes, CHROMA_444, W, tag, flags);
 }
 
 // 4:2:0 frames through the ring (SURVEY.md 8(f) rank 4 at the asynchronous boundary): half the PCIe
@@ -3011,7 +3175,35 @@ int ffv2amd_ring_send_420(ffv2amd_encoder *e, const uint8_t *const data[3], cons
         RingPlane{ data[1], linesize[1], (size_t)cw * bps, c_pitch, ch, 1, r.d_c420, cst },
         RingPlane{ data[2], linesize[2], (size_t)cw * bps, c_pitch, ch, 1, r.d_c420 + c_pitch * (size_t)ch, cst + c_pitch * (size_t)ch },
     };
-    return ring_submit(e, r, pl, 3, true, W, tag, flags);
+    return ring_submit(e, r, pl, 3, CHROMA_420, W, tag, flags);
+}
+
+// 4:2:2 frames through the ring: two thirds of the PCIe bytes of the 4:4:4 form.  As ring_send_420, with
+// chroma staging h rows high and the up-conversion along x only (ffv2_upconv.hip).
+int ffv2amd_ring_send_422(ffv2amd_encoder *e, const uint8_t *const data[3], const ptrdiff_t linesize[3],
+                          const int32_t *W, int64_t tag, unsigned flags)
+{
+    if (!e || !data || !linesize || e->ring.empty() || !data[0] || !data[1] || !data[2]) return FFV2AMD_ERR_INVAL;
+    if (e->ring_count == (int)e->ring.size()) return FFV2AMD_ERR_AGAIN;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return FFV2AMD_ERR_DEVICE;
+    int rc = upconv422_ready(e);
+    if (rc < 0) return rc;
+    const ffv2amd_info &in = e->info;
+    const size_t bps = in.depth > 8 ? 2 : 1;
+    const int cw = (in.width + 1) >> 1, ch = in.height;
+    const size_t c_pitch = align_up((size_t)cw * bps, 128);
+    auto &r = e->ring[(size_t)((e->ring_head + e->ring_count) % (int)e->ring.size())];
+    if (!r.d_c422) HIPCHK(hipMalloc(&r.d_c422, 2 * c_pitch * (size_t)ch));
+    // pinned staging of a pageable frame: luma in plane 0 of the slot's host frame, U and V behind it
+    // (2 * h * c_pitch <= 2 * h * row_pitch: they fit planes 1 and 2)
+    uint8_t *cst = r.h_frame + in.plane_stride;
+    RingPlane pl[3] = {
+        RingPlane{ data[0], linesize[0], (size_t)in.width * bps, in.row_pitch, in.height, 4, r.d_frame, r.h_frame },
+        RingPlane{ data[1], linesize[1], (size_t)cw * bps, c_pitch, ch, 2, r.d_c422, cst },
+        RingPlane{ data[2], linesize[2], (size_t)cw * bps, c_pitch, ch, 2, r.d_c422 + c_pitch * (size_t)ch, cst + c_pitch * (size_t)ch },
+    };
+    return ring_submit(e, r, pl, 3, CHROMA_422, W, tag, flags);
 }
 
 int ffv2amd_ring_receive(ffv2amd_encoder *e, uint8_t *out, size_t out_cap, size_t *out_size, int64_t *tag, int wait)

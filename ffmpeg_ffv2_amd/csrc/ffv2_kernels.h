@@ -86,6 +86,17 @@ hipError_t ffv2_launch_upconv(const FFV2Upconv *u, const FFV2Geom &g, int nframe
 hipError_t ffv2_launch_upconv_chroma(const FFV2Upconv *u, const FFV2Geom &g, int nframes, const uint8_t *src_u,
                                      size_t c_pitch, size_t c_plane_stride, size_t src_frame_stride, uint8_t *dst,
                                      hipStream_t s);
+// 4:2:2 -> 4:4:4 (ffv2_upconv.hip): the horizontal table only, any height
+struct FFV2Upconv422;
+FFV2Upconv422 *ffv2_upconv422_create(int w, int depth, hipStream_t s);
+void ffv2_upconv422_destroy(FFV2Upconv422 *u);
+size_t ffv2_upconv422_src_frame_bytes(int w, int h, int depth);
+bool ffv2_upconv422_uses_strips(const FFV2Upconv422 *u);   // which kernel the next launch takes
+hipError_t ffv2_launch_upconv422(const FFV2Upconv422 *u, const FFV2Geom &g, int nframes, const uint8_t *src,
+                                 size_t src_frame_stride, uint8_t *dst, hipStream_t s);
+hipError_t ffv2_launch_upconv422_chroma(const FFV2Upconv422 *u, const FFV2Geom &g, int nframes, const uint8_t *src_u,
+                                        size_t c_pitch, size_t c_plane_stride, size_t src_frame_stride, uint8_t *dst,
+                                        hipStream_t s);
 
 // qp > 0 entropy coder on the device (ffv2_rangecoder.hip): one wavefront per frame
 struct FFV2RangeCoderArgs {

@@ -402,3 +402,263 @@ hipError_t ffv2_launch_upconv(const FFV2Upconv *u, const FFV2Geom &g, int nframe
     return ffv2_launch_upconv_chroma(u, g, nframes, src + (size_t)g.width * g.height * bps, cw * bps, cw * ch * bps,
                                      src_frame_stride, dst, s);
 }
+
+// =============================================================================================
+// 4:2:2 -> 4:4:4.  For a yuv422p / yuv422p10le / yuv422p12le source the tool chain does the same
+// thing as for 4:2:0 with one axis less:
+//   format   av_find_best_pix_fmt_of_2 / get_pix_fmt_score (libavutil/pixdesc.c:2838-2873) pick
+//            yuv444p* of the same depth (no loss; ties go to the smaller format);
+//   scaler   ff_get_unscaled_swscale has no converter for the pair, the subsampling differs
+//            (swscale_unscaled.c:2122-2137): the generic scaler runs;
+//   chroma x vf_scale's default chroma position -513 (the YUV420P override, vf_scale.c:566-572,
+//            does not apply) becomes 128 on a subsampled axis (get_local_pos, utils.c:303-310): the
+//            horizontal filter is the 4:2:0 one, build_axis(w, 1 << 14) over ceil(w/2) samples;
+//            h = min((sum s * hf) >> (8-bit: 7 | deeper: depth-1), 32767)   (swscale.c:96-139)
+//   chroma y not subsampled: src pos = dst pos = 128, chrYInc = 1 << 16, so initFilter's unscaled
+//            branch (utils.c:353-362) gives filter size 1 and vscale.c:274,90-91 calls yuv2plane1:
+//              8 bit:  out = clip_u8((h + 64) >> 7)   (constant dither 64: 8-bit sources are not
+//                      dithered, swscale.c:263,346; output.c:395-403)
+//              deeper: out = clip((h + (1 << (14-d))) >> (15-d), 0, 2^d - 1)   (output.c:320-330)
+//   luma     the identity.
+// Because initFilter normalises every vertical row to exactly 4096, the 4:2:0 path fed chroma that
+// is constant along y gives this result in every row -- the tests tie the two together that way.
+// PARITY UNPINNED, as for 4:2:0: no libswscale binary or vector exists here.
+//
+// Device part: every output row depends on one source row, so there is no LDS transpose and no
+// vertical pass: ffv2_upconv422_kernel is a streaming 2x horizontal bicubic.  A wave owns a
+// 64 * (16 / bytes per sample) wide strip of one row at a time: its source span (coalesced loads)
+// goes to LDS, each lane then writes one 16-byte vector of consecutive output samples from its
+// 4 taps per sample; the lane's positions and coefficients stay in registers for the 4 rows the
+// wave does.  ffv2_upconv422_naive_kernel (one thread per sample, any tap count) is the fallback
+// for tables the strip does not fit -- none that build_axis makes for w >= 12 -- and can be forced
+// with FFV2AMD_UPCONV422_NAIVE=1 (read per launch).
+// =============================================================================================
+namespace {
+
+template <int BPS> struct U2Shape {
+    static constexpr int VEC = 16 / BPS;       // output samples per lane: one 16-byte store
+    static constexpr int TW = 64 * VEC;        // output columns per strip
+    static constexpr int SPAN = TW / 2 + 32;   // source samples a strip may read (checked on the host)
+    static constexpr int LOADS = (SPAN + 63) / 64;   // loads per lane and source row
+    static constexpr int RW = BPS == 2 ? 8 : 4;      // rows per wave: all their loads are in flight at once
+    static constexpr int ROWS = 4 * RW;              // output rows per workgroup
+};
+
+struct Up422Args {
+    const uint8_t *src;        // U plane of frame 0; V at + c_plane_stride, frame f at + f * src_frame_stride
+    uint8_t *dst;              // [nframes][frame_stride]: the encoder's 4:4:4 layout
+    size_t src_frame_stride, c_plane_stride, c_pitch;     // bytes
+    size_t frame_stride, plane_stride, row_pitch;
+    int w, h, cw, depth, htaps;
+    const int16_t *hf;         // [w][UP_TAPS], zero beyond htaps
+    const int32_t *hp;         // [w]
+};
+
+// the vertical no-op of yuv2plane1: 15-bit intermediate -> output sample.  The intermediate is an int16_t in
+// swscale (hScale*To15's dst): a sum below -32768, which only samples above the depth reach, wraps.
+template <int BPS>
+__device__ __forceinline__ int u2_out(int hv, int depth)
+{
+    hv = (int16_t)(hv < 32767 ? hv : 32767);
+    const int v = BPS == 1 ? (hv + 64) >> 7 : (hv + (1 << (14 - depth))) >> (15 - depth);
+    const int hi = (1 << depth) - 1;
+    return v < 0 ? 0 : (v > hi ? hi : v);
+}
+
+template <int BPS>
+__global__ __launch_bounds__(256) void ffv2_upconv422_kernel(const Up422Args a)
+{
+    using S = U2Shape<BPS>;
+    constexpr int VEC = S::VEC, TW = S::TW, SPAN = S::SPAN, RW = S::RW;
+    __shared__ uint16_t span[4][RW][SPAN];     // [wave][row]
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int x0 = blockIdx.x * TW, yw = blockIdx.y * S::ROWS + wv * RW;    // the wave's rows: yw .. yw + RW - 1
+    const int p = 1 + (int)(blockIdx.z & 1u), f = (int)(blockIdx.z >> 1);
+    const int xl = min(x0 + TW, a.w) - 1;
+    const int s0 = a.hp[x0], ns = min(a.hp[xl] + a.htaps, a.cw) - s0;      // source columns [s0, s0 + ns)
+    const uint8_t *sp = a.src + (size_t)f * a.src_frame_stride + (size_t)(p - 1) * a.c_plane_stride + (size_t)s0 * BPS;
+    // the source spans of the wave's rows -> LDS, four rows at a time: the loads are unconditional (indices clamped
+    // into the span and the picture) so that all of them are in flight before the first is waited for
+#pragma unroll
+    for (int j0 = 0; j0 < RW; j0 += 4) {
+        uint32_t v[4][S::LOADS];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint8_t *row = sp + (size_t)min(yw + j0 + j, a.h - 1) * a.c_pitch;
+#pragma unroll
+            for (int k = 0; k < S::LOADS; k++) {
+                const int i = min(lane + 64 * k, ns - 1);
+                v[j][k] = BPS == 1 ? row[i] : reinterpret_cast<const uint16_t *>(row)[i];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int k = 0; k < S::LOADS; k++)
+                if (lane + 64 * k < ns) span[wv][j0 + j][lane + 64 * k] = (uint16_t)v[j][k];
+    }
+    // this lane's VEC outputs: positions relative to s0, 4 coefficients each (zero beyond htaps)
+    const int x = x0 + lane * VEC;
+    int pos[VEC];
+    uint2 cf[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; e++) {
+        const int xe = min(x + e, xl);
+        pos[e] = a.hp[xe] - s0;
+        cf[e] = *reinterpret_cast<const uint2 *>(a.hf + (size_t)xe * UP_TAPS);
+    }
+    __syncthreads();
+    if (x >= a.w) return;
+    const int hsh = BPS == 1 ? 7 : a.depth - 1;
+    uint8_t *dp = a.dst + (size_t)f * a.frame_stride + (size_t)p * a.plane_stride + (size_t)x * BPS;
+#pragma unroll 2
+    for (int j = 0; j < RW; j++) {
+        const int y = yw + j;
+        if (y >= a.h) break;
+        int o[VEC];
+#pragma unroll
+        for (int e = 0; e < VEC; e++) {
+            const uint16_t *s = &span[wv][j][pos[e]];
+            const int hv = (int)s[0] * ((int)(cf[e].x << 16) >> 16) + (int)s[1] * ((int)cf[e].x >> 16) +
+                           (int)s[2] * ((int)(cf[e].y << 16) >> 16) + (int)s[3] * ((int)cf[e].y >> 16);
+            o[e] = u2_out<BPS>(hv >> hsh, a.depth);
+        }
+        // the row pitch is a multiple of 128 bytes: a whole vector may be written where the picture
+        // ends inside it (the padding behind the last sample is never read as picture)
+        uint4 v;
+        if constexpr (BPS == 1) {
+            v = make_uint4((uint32_t)o[0] | ((uint32_t)o[1] << 8) | ((uint32_t)o[2] << 16) | ((uint32_t)o[3] << 24),
+                           (uint32_t)o[4] | ((uint32_t)o[5] << 8) | ((uint32_t)o[6] << 16) | ((uint32_t)o[7] << 24),
+                           (uint32_t)o[8] | ((uint32_t)o[9] << 8) | ((uint32_t)o[10] << 16) | ((uint32_t)o[11] << 24),
+                           (uint32_t)o[12] | ((uint32_t)o[13] << 8) | ((uint32_t)o[14] << 16) | ((uint32_t)o[15] << 24));
+        } else {
+            v = make_uint4((uint32_t)o[0] | ((uint32_t)o[1] << 16), (uint32_t)o[2] | ((uint32_t)o[3] << 16),
+                           (uint32_t)o[4] | ((uint32_t)o[5] << 16), (uint32_t)o[6] | ((uint32_t)o[7] << 16));
+        }
+        *reinterpret_cast<uint4 *>(dp + (size_t)y * a.row_pitch) = v;
+    }
+}
+
+// one thread per output sample, any tap count up to UP_TAPS, taps read from global memory
+template <int BPS>
+__global__ __launch_bounds__(256) void ffv2_upconv422_naive_kernel(const Up422Args a)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    const int p = 1 + (int)(blockIdx.z & 1u), f = (int)(blockIdx.z >> 1);
+    if (x >= a.w) return;
+    const uint8_t *row = a.src + (size_t)f * a.src_frame_stride + (size_t)(p - 1) * a.c_plane_stride + (size_t)y * a.c_pitch;
+    const int hp = a.hp[x];
+    int hv = 0;
+    for (int k = 0; k < a.htaps; k++) {
+        const int s = BPS == 1 ? row[hp + k] : reinterpret_cast<const uint16_t *>(row)[hp + k];
+        hv += s * a.hf[(size_t)x * UP_TAPS + k];
+    }
+    const int v = u2_out<BPS>(hv >> (BPS == 1 ? 7 : a.depth - 1), a.depth);
+    uint8_t *dp = a.dst + (size_t)f * a.frame_stride + (size_t)p * a.plane_stride + (size_t)y * a.row_pitch;
+    if (BPS == 1) dp[x] = (uint8_t)v;
+    else reinterpret_cast<uint16_t *>(dp)[x] = (uint16_t)v;
+}
+
+}  // namespace
+
+struct FFV2Upconv422 {
+    int w = 0, depth = 0, htaps = 0;
+    bool strips = false;       // every strip's source span fits ffv2_upconv422_kernel's LDS
+    int16_t *d_hf = nullptr;
+    int32_t *d_hp = nullptr;
+};
+
+void ffv2_upconv422_destroy(FFV2Upconv422 *u)
+{
+    if (!u) return;
+    (void)hipFree(u->d_hf); (void)hipFree(u->d_hp);
+    delete u;
+}
+
+// the horizontal table of a w-wide picture (any height); nullptr where that axis does not build --
+// the horizontal half of ffv2_upconv_create's rule.  Uploaded on `s`, which is waited for.
+FFV2Upconv422 *ffv2_upconv422_create(int w, int depth, hipStream_t s)
+{
+    AxisFilter hx;
+    try {
+        if (!build_axis(hx, w, 1 << 14)) return nullptr;                     // :1681
+    } catch (...) { return nullptr; }
+    FFV2Upconv422 *u = new (std::nothrow) FFV2Upconv422;
+    if (!u) return nullptr;
+    u->w = w; u->depth = depth; u->htaps = hx.taps;
+    {
+        const int cw = (w + 1) >> 1;
+        const int tw = depth > 8 ? U2Shape<2>::TW : U2Shape<1>::TW, span = depth > 8 ? U2Shape<2>::SPAN : U2Shape<1>::SPAN;
+        bool fits = hx.taps <= 4;
+        for (int x0 = 0; x0 < w && fits; x0 += tw) {
+            const int xl = (x0 + tw < w ? x0 + tw : w) - 1;
+            int c1 = hx.pos[(size_t)xl] + hx.taps;
+            if (c1 > cw) c1 = cw;
+            // the strip's span plus the 4-tap reads of its last sample stay inside the LDS row
+            fits = hx.pos[(size_t)x0] >= 0 && c1 - hx.pos[(size_t)x0] + 4 <= span &&
+                   hx.pos[(size_t)xl] - hx.pos[(size_t)x0] + 4 <= span;
+            for (int x = x0; x <= xl && fits; x++) fits = hx.pos[(size_t)x] >= hx.pos[(size_t)x0] && hx.pos[(size_t)x] <= hx.pos[(size_t)xl];
+        }
+        u->strips = fits;
+    }
+    bool ok = hipMalloc(&u->d_hf, hx.coef.size() * 2) == hipSuccess && hipMalloc(&u->d_hp, hx.pos.size() * 4) == hipSuccess;
+    ok = ok && hipMemcpyAsync(u->d_hf, hx.coef.data(), hx.coef.size() * 2, hipMemcpyHostToDevice, s) == hipSuccess &&
+         hipMemcpyAsync(u->d_hp, hx.pos.data(), hx.pos.size() * 4, hipMemcpyHostToDevice, s) == hipSuccess &&
+         hipStreamSynchronize(s) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); ffv2_upconv422_destroy(u); return nullptr; }
+    return u;
+}
+
+size_t ffv2_upconv422_src_frame_bytes(int w, int h, int depth)
+{
+    const size_t bps = depth > 8 ? 2 : 1;
+    return ((size_t)w * h + 2 * (size_t)((w + 1) >> 1) * h) * bps;
+}
+
+bool ffv2_upconv422_uses_strips(const FFV2Upconv422 *u)
+{
+    const char *force = getenv("FFV2AMD_UPCONV422_NAIVE");
+    return u->strips && !(force && atoi(force));
+}
+
+// chroma planes only: src_u = U plane of frame 0 (h rows, c_pitch bytes apart), V at + c_plane_stride, the
+// next frame at + src_frame_stride; dst = the encoder's 4:4:4 frames (planes 1 and 2 are written)
+hipError_t ffv2_launch_upconv422_chroma(const FFV2Upconv422 *u, const FFV2Geom &g, int nframes, const uint8_t *src_u,
+                                        size_t c_pitch, size_t c_plane_stride, size_t src_frame_stride, uint8_t *dst,
+                                        hipStream_t s)
+{
+    const int bps = g.bytes_per_sample;
+    Up422Args a{};
+    a.src = src_u; a.dst = dst; a.src_frame_stride = src_frame_stride; a.c_plane_stride = c_plane_stride; a.c_pitch = c_pitch;
+    a.frame_stride = g.frame_stride; a.plane_stride = g.plane_stride; a.row_pitch = g.row_pitch;
+    a.w = g.width; a.h = g.height; a.cw = (g.width + 1) >> 1; a.depth = g.depth;
+    a.htaps = u->htaps; a.hf = u->d_hf; a.hp = u->d_hp;
+    if (ffv2_upconv422_uses_strips(u)) {
+        const int tw = bps == 1 ? U2Shape<1>::TW : U2Shape<2>::TW;
+        const int rows = bps == 1 ? U2Shape<1>::ROWS : U2Shape<2>::ROWS;
+        const dim3 grid((unsigned)((g.width + tw - 1) / tw), (unsigned)((g.height + rows - 1) / rows), (unsigned)(2 * nframes)), block(256);
+        if (bps == 1) hipLaunchKernelGGL(ffv2_upconv422_kernel<1>, grid, block, 0, s, a);
+        else          hipLaunchKernelGGL(ffv2_upconv422_kernel<2>, grid, block, 0, s, a);
+    } else {
+        const dim3 grid((unsigned)((g.width + 255) / 256), (unsigned)g.height, (unsigned)(2 * nframes)), block(256);
+        if (bps == 1) hipLaunchKernelGGL(ffv2_upconv422_naive_kernel<1>, grid, block, 0, s, a);
+        else          hipLaunchKernelGGL(ffv2_upconv422_naive_kernel<2>, grid, block, 0, s, a);
+    }
+    return hipGetLastError();
+}
+
+// tightly packed 4:2:2 frames (Y, U, V back to back) -> 4:4:4 frames
+hipError_t ffv2_launch_upconv422(const FFV2Upconv422 *u, const FFV2Geom &g, int nframes, const uint8_t *src,
+                                 size_t src_frame_stride, uint8_t *dst, hipStream_t s)
+{
+    const int bps = g.bytes_per_sample;
+    for (int f = 0; f < nframes; f++) {       // luma: the identity
+        const hipError_t rc = hipMemcpy2DAsync(dst + (size_t)f * g.frame_stride, g.row_pitch, src + (size_t)f * src_frame_stride,
+                                               (size_t)g.width * bps, (size_t)g.width * bps, (size_t)g.height,
+                                               hipMemcpyDeviceToDevice, s);
+        if (rc != hipSuccess) return rc;
+    }
+    const size_t cw = (size_t)((g.width + 1) >> 1);
+    return ffv2_launch_upconv422_chroma(u, g, nframes, src + (size_t)g.width * g.height * bps, cw * bps, cw * g.height * bps,
+                                        src_frame_stride, dst, s);
+}

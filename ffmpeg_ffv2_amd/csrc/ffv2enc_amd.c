@@ -183,6 +183,32 @@ int ffv2amd_codec_encode_yuv420(FFV2AMDCodecContext *avctx, FFV2AMDPacket *avpkt
     return 0;
 }
 
+/* The same for a yuv422p / yuv422p10le / yuv422p12le source: av_find_best_pix_fmt_of_2
+ * (libavutil/pixdesc.c:2838-2873) selects yuv444p* of the same depth, libswscale's generic scaler
+ * converts (chroma 2x up along x only), then encode2() runs.  PARITY UNPINNED. */
+int ffv2amd_codec_encode_yuv422(FFV2AMDCodecContext *avctx, FFV2AMDPacket *avpkt,
+                                const FFV2AMDFrame *frame, int *got_packet_ptr)
+{
+    FFV2AMDEncCtx *s;
+    size_t n = 0;
+    int ret;
+    if (!avctx || !avctx->priv_data || !avpkt || !frame || !got_packet_ptr)
+        return FFV2AMD_ERR_INVAL;
+    s = avctx->priv_data;
+    *got_packet_ptr = 0;
+    if (avctx->global_quality > 0 && s->scratch_cap < s->info.packet_cap_qp)
+        return FFV2AMD_ERR_NOSPACE;
+    ret = ffv2amd_encode_frame_422(s->enc, frame->data, frame->linesize, avctx->global_quality,
+                                   s->scratch, s->scratch_cap, &n);
+    if (ret < 0)
+        return ret;
+    ret = hand_over(s, avpkt, n, frame->pts);
+    if (ret < 0)
+        return ret;
+    *got_packet_ptr = 1;
+    return 0;
+}
+
 /* avcodec_send_frame / avcodec_receive_packet (encode.c:420,449): the caller is ONE thread feeding
  * frames and collecting packets; frames are independent (ffv2enc.c:461-469), so frame n goes to
  * device n % ndev -- each device has its own encoder and asynchronous ring (global_quality 0) or
@@ -194,6 +220,8 @@ int ffv2amd_codec_send_frame(FFV2AMDCodecContext *avctx, const FFV2AMDFrame *fra
     const int qp = avctx ? avctx->global_quality : 0;
     int ret, mode;
     if (!avctx || !avctx->priv_data || qp < 0)
+        return FFV2AMD_ERR_INVAL;
+    if ((flags & FFV2AMD_FRAME_YUV420) && (flags & FFV2AMD_FRAME_YUV422))
         return FFV2AMD_ERR_INVAL;
     s = avctx->priv_data;
     if (!frame) {                               /* end of stream: batches that are not full yet go out */
@@ -223,10 +251,12 @@ int ffv2amd_codec_send_frame(FFV2AMDCodecContext *avctx, const FFV2AMDFrame *fra
             s->qpring_qp = qp;
         }
         ret = ffv2amd_qpring_send(enc, frame->data, frame->linesize, NULL, frame->pts,
-                                  flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_YUV420 | FFV2AMD_FRAME_REGISTER));
+                                  flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_YUV420 | FFV2AMD_FRAME_YUV422 | FFV2AMD_FRAME_REGISTER));
     } else if (mode == 2) {
         ret = flags & FFV2AMD_FRAME_YUV420
             ? ffv2amd_qp_send_frame_420(enc, frame->data, frame->linesize, qp, frame->pts)
+            : flags & FFV2AMD_FRAME_YUV422
+            ? ffv2amd_qp_send_frame_422(enc, frame->data, frame->linesize, qp, frame->pts)
             : ffv2amd_qp_send_frame(enc, frame->data, frame->linesize, qp, NULL, frame->pts);
     } else {
         if (!s->ring_open) {
@@ -240,6 +270,8 @@ int ffv2amd_codec_send_frame(FFV2AMDCodecContext *avctx, const FFV2AMDFrame *fra
         }
         ret = flags & FFV2AMD_FRAME_YUV420
             ? ffv2amd_ring_send_420(enc, frame->data, frame->linesize, NULL, frame->pts, flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_REGISTER))
+            : flags & FFV2AMD_FRAME_YUV422
+            ? ffv2amd_ring_send_422(enc, frame->data, frame->linesize, NULL, frame->pts, flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_REGISTER))
             : ffv2amd_ring_send(enc, frame->data, frame->linesize, NULL, frame->pts, flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_REGISTER));
     }
     if (ret < 0)

@@ -215,6 +215,38 @@ class FFV2Encoder:
                    "ffv2amd_upconvert_420_device")
         return self.unpack_frames(dst.cpu().numpy())[0]
 
+    # -- 4:2:2 front end (libswscale's generic scaler: chroma 2x up along x only) --
+    def _planes422(self, y, u, v):
+        i = self.info
+        cw = (i.width + 1) // 2
+        y = np.ascontiguousarray(y, self.dtype); u = np.ascontiguousarray(u, self.dtype); v = np.ascontiguousarray(v, self.dtype)
+        assert y.shape == (i.height, i.width) and u.shape == (i.height, cw) and v.shape == (i.height, cw), (y.shape, u.shape)
+        return y, u, v
+
+    def encode2_422(self, y, u, v, qp=0):
+        """yuv422p* host frame (Y (H,W); U, V (H, ceil(W/2))) -> packet bytes."""
+        y, u, v = self._planes422(y, u, v)
+        data = (C.c_void_p * 3)(y.ctypes.data, u.ctypes.data, v.ctypes.data)
+        ls = (C.c_ssize_t * 3)(y.strides[0], u.strides[0], v.strides[0])
+        out = np.empty(self.info.packet_cap if qp == 0 else self.info.packet_cap_qp, np.uint8)
+        n = C.c_size_t(0)
+        _lib.check(self._lib.ffv2amd_encode_frame_422(self._h, data, ls, qp, out.ctypes.data_as(C.c_void_p), out.size,
+                                                      C.byref(n)), "ffv2amd_encode_frame_422")
+        return out[: n.value].tobytes()
+
+    def upconvert_422(self, y, u, v):
+        """-> (3,H,W) yuv444p* samples as the GPU front end produces them."""
+        import torch
+        y, u, v = self._planes422(y, u, v)
+        src = torch.from_numpy(np.concatenate([y.reshape(-1), u.reshape(-1), v.reshape(-1)]).view(np.uint8)).to(
+            "cuda:%d" % self.device)
+        assert src.numel() == self._lib.ffv2amd_frame_bytes_422(self._h)
+        dst = torch.zeros((1, self.info.frame_stride), dtype=torch.uint8, device=src.device)
+        stream = torch.cuda.current_stream(src.device).cuda_stream
+        _lib.check(self._lib.ffv2amd_upconvert_422_device(self._h, 1, src.data_ptr(), dst.data_ptr(), C.c_void_p(stream)),
+                   "ffv2amd_upconvert_422_device")
+        return self.unpack_frames(dst.cpu().numpy())[0]
+
     def set_device_coder(self, on=True):
         """qp > 0: run the adaptive range coder on the device (one wavefront per frame) instead of host threads."""
         _lib.check(self._lib.ffv2amd_encoder_set_device_coder(self._h, 1 if on else 0), "set_device_coder")
@@ -479,6 +511,43 @@ class FFV2Encoder:
             out.append((yy, uu, vv))
         return out
 
+    def ring_send_422(self, y, u, v, tag=0, pinned=False, register=False):
+        """A yuv422p* frame through the ring (Y (H,W); U, V (H, ceil(W/2)), any row stride): two thirds of the
+        PCIe bytes of its 4:4:4 form, up-converted on the frame's compute stream.  False when the ring is full."""
+        i = self.info
+        cw = (i.width + 1) // 2
+        for a, shp in ((y, (i.height, i.width)), (u, (i.height, cw)), (v, (i.height, cw))):
+            assert a.dtype == self.dtype and a.shape == shp and a.strides[1] == self.dtype.itemsize, (a.dtype, a.shape)
+        data = (C.c_void_p * 3)(y.ctypes.data, u.ctypes.data, v.ctypes.data)
+        ls = (C.c_ssize_t * 3)(y.strides[0], u.strides[0], v.strides[0])
+        r = self._lib.ffv2amd_ring_send_422(self._h, data, ls, None, int(tag), (1 if pinned else 0) | (4 if register else 0))
+        if r == -11:
+            return False
+        _lib.check(r, "ring_send_422")
+        return True
+
+    def pinned_frames_422(self, count):
+        """count page-locked yuv422p* frames as a list of (Y, U, V) sample arrays whose row strides equal the
+        device pitches, for ring_send_422(pinned=True).  Free with free_pinned()."""
+        i = self.info
+        bps = self.dtype.itemsize
+        cw = (i.width + 1) // 2
+        cp = (cw * bps + 127) // 128 * 128
+        per = i.row_pitch * i.height + 2 * cp * i.height
+        ptr = self._lib.ffv2amd_host_alloc(count * per)
+        if not ptr:
+            raise MemoryError("ffv2amd_host_alloc(%d)" % (count * per))
+        self._pinned = getattr(self, "_pinned", []) + [ptr]
+        buf = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * per,))
+        out = []
+        for n in range(count):
+            b = buf[n * per: (n + 1) * per]
+            yy = b[: i.row_pitch * i.height].reshape(i.height, i.row_pitch).view(self.dtype)[:, : i.width]
+            uu = b[i.row_pitch * i.height:][: cp * i.height].reshape(i.height, cp).view(self.dtype)[:, : cw]
+            vv = b[i.row_pitch * i.height + cp * i.height:][: cp * i.height].reshape(i.height, cp).view(self.dtype)[:, : cw]
+            out.append((yy, uu, vv))
+        return out
+
     def ring_receive(self, wait=True):
         """-> (tag, packet bytes) of the oldest frame in flight, or None (nothing in flight /
         wait=False and not finished yet).  A failed frame raises FFV2Error."""
@@ -497,11 +566,11 @@ class FFV2Encoder:
         cap = packet_cap or self.info.packet_cap_qp
         self._qpring_out = np.empty(int(cap) + 16, np.uint8)
 
-    def qpring_send(self, frame, tag=0, W=None, pinned=False, yuv420=False, register=False):
-        """frame: (P,H,W) host array, or with yuv420=True the (Y, U, V) arrays of a yuv420p* frame.  False: EAGAIN
-        (receive packets first, then send the frame again)."""
+    def qpring_send(self, frame, tag=0, W=None, pinned=False, yuv420=False, register=False, yuv422=False):
+        """frame: (P,H,W) host array, or with yuv420=True / yuv422=True the (Y, U, V) arrays of a yuv420p* / yuv422p*
+        frame.  False: EAGAIN (receive packets first, then send the frame again)."""
         i = self.info
-        planes = list(frame) if yuv420 else [frame[p] for p in range(i.planes)]
+        planes = list(frame) if yuv420 or yuv422 else [frame[p] for p in range(i.planes)]
         data = (C.c_void_p * 4)()
         ls = (C.c_ssize_t * 4)()
         for p, a in enumerate(planes):
@@ -514,7 +583,8 @@ class FFV2Encoder:
             assert W.size == i.block_planes
             wp = W.ctypes.data_as(C.c_void_p)
         r = self._lib.ffv2amd_qpring_send(self._h, data, ls, wp, int(tag),
-                                          (1 if pinned else 0) | (2 if yuv420 else 0) | (4 if register else 0))
+                                          (1 if pinned else 0) | (2 if yuv420 else 0) | (4 if register else 0) |
+                                          (8 if yuv422 else 0))
         if r == -11:
             return False
         _lib.check(r, "qpring_send")

@@ -156,6 +156,25 @@ int  ffv2amd_upconvert_420_device(ffv2amd_encoder *enc, int nframes, const void 
 int  ffv2amd_encode_frame_420(ffv2amd_encoder *enc, const uint8_t *const data[3], const ptrdiff_t linesize[3],
                               int qp, uint8_t *out, size_t out_cap, size_t *out_size);
 
+/* 4:2:2 front end: the same step for yuv422p / yuv422p10le / yuv422p12le.  av_find_best_pix_fmt_of_2 /
+ * get_pix_fmt_score (libavutil/pixdesc.c:2838-2873) pick yuv444p* of the same depth; libswscale has no
+ * unscaled converter for the pair (swscale_unscaled.c:2122-2137), so its generic scaler runs: luma
+ * unchanged, chroma 2x up along x with the 4:2:0 path's horizontal bicubic (get_local_pos, utils.c:303-310)
+ * and unscaled along y (initFilter's filter size 1, utils.c:353-362; yuv2plane1, output.c:320-330,395-403).
+ * Encoder: the yuv444p format of the same depth, otherwise FFV2AMD_ERR_INVAL; FFV2AMD_ERR_UNSUPPORTED
+ * where the horizontal filter does not build.  PARITY UNPINNED (no libswscale binary or vector here).
+ *   4:2:2 frames are tightly packed: Y (w x h), U, V (ceil(w/2) x h), uint8 or uint16le,
+ *   ffv2amd_frame_bytes_422() bytes each (0 for a NULL encoder).
+ *   upconvert_422_device : nframes such frames in device memory -> the encoder's 4:4:4 frame layout, on `stream`.
+ *   encode_frame_422     : one host frame (data[0..2] = Y, U, V with their own linesizes) -> packet, any qp;
+ *                          a frame with samples above the declared depth is rerun by the wide T-stage, as in
+ *                          ffv2amd_encode_frame_420. */
+size_t ffv2amd_frame_bytes_422(const ffv2amd_encoder *enc);
+int  ffv2amd_upconvert_422_device(ffv2amd_encoder *enc, int nframes, const void *d_src422,
+                                  void *d_frames444, void *stream);
+int  ffv2amd_encode_frame_422(ffv2amd_encoder *enc, const uint8_t *const data[3], const ptrdiff_t linesize[3],
+                              int qp, uint8_t *out, size_t out_cap, size_t *out_size);
+
 /* The same batch step for 1 <= qp <= 64 split in two, so that consecutive batches overlap:
  *   qp_submit : T-stage, PVQ search and symbol compaction of one batch, asynchronous on the
  *               encoder's stream (frames must be complete when it is called); at most two
@@ -181,6 +200,8 @@ int  ffv2amd_qp_send_frame(ffv2amd_encoder *enc, const uint8_t *const data[4], c
                            int qp, const int32_t *W, int64_t tag);
 /* a yuv420p* frame (Y, U, V) through the same pipeline, up-converted on the device first (see ffv2amd_ring_send_420) */
 int  ffv2amd_qp_send_frame_420(ffv2amd_encoder *enc, const uint8_t *const data[3], const ptrdiff_t linesize[3], int qp, int64_t tag);
+/* a yuv422p* frame (Y, U, V) the same way (see ffv2amd_encode_frame_422) */
+int  ffv2amd_qp_send_frame_422(ffv2amd_encoder *enc, const uint8_t *const data[3], const ptrdiff_t linesize[3], int qp, int64_t tag);
 int  ffv2amd_qp_receive_packet(ffv2amd_encoder *enc, uint8_t *out, size_t out_cap, size_t *out_size, int64_t *tag);
 int  ffv2amd_qp_pending(const ffv2amd_encoder *enc);
 
@@ -202,7 +223,8 @@ int  ffv2amd_qp_pending(const ffv2amd_encoder *enc);
  *   qpring_send    : flags FFV2AMD_FRAME_PINNED (planes page-locked and untouched until the frame's packet has
  *                    been received: the DMA engine reads them in place), FFV2AMD_FRAME_REGISTER (the same promise for
  *                    ordinary memory from a pool of long-lived buffers, page-locked here on first sight) and/or
- *                    FFV2AMD_FRAME_YUV420 (data = Y, U, V of a yuv420p* frame); otherwise the rows are copied before
+ *                    FFV2AMD_FRAME_YUV420 (data = Y, U, V of a yuv420p* frame) or FFV2AMD_FRAME_YUV422 (of a
+ *                    yuv422p* frame; both at once is FFV2AMD_ERR_INVAL) -- one batch may mix the three; otherwise the rows are copied before
  *                    the call returns (into about 256 MB of page-locked bounce frames the ring owns, by helper
  *                    threads as in ring_send: FFV2AMD_GATHER_THREADS).
  *                    FFV2AMD_ERR_AGAIN: a batch is full, two calls are in flight and the packets of the one
@@ -285,6 +307,11 @@ void   ffv2amd_debug_lanecoder_window(uint32_t symbols);
 /* Benchmark aid: the Q-stage (PVQ search) kernel alone on `nframes` (<= max_batch) device-resident frames:
  * average ms per launch over `reps` launches (bench.py --qp reports it against the f32 division rate). */
 int    ffv2amd_debug_pvq_time(ffv2amd_encoder *enc, int nframes, const void *d_frames, int qp, int reps, float *ms_per_launch);
+/* Benchmark aid: the 4:2:2 chroma up-conversion kernel alone (no luma copy) on `nframes` tightly packed 4:2:2
+ * frames in device memory (see ffv2amd_upconvert_422_device), on the encoder's stream after one warm-up launch:
+ * average ms per launch over `reps` launches (tools/bench_422.py). */
+int    ffv2amd_debug_upconv422_time(ffv2amd_encoder *enc, int nframes, const void *d_src422, void *d_frames444, int reps,
+                                    float *ms_per_launch);
 int    ffv2amd_lanecoder_encode(ffv2amd_encoder *enc, int nframes, const void *d_frames, int qp,
                                 const int32_t *d_W, uint8_t *h_packets, size_t packet_stride,
                                 uint32_t *h_sizes, int32_t *h_status);
@@ -358,6 +385,8 @@ int  ffv2amd_encoder_flush(ffv2amd_encoder *enc, void *stream);
  *                  (status < 0) is dropped from the ring and its error returned. */
 #define FFV2AMD_FRAME_PINNED 1u
 #define FFV2AMD_FRAME_YUV420 2u      /* ffv2amd_codec_send_frame only: a 4:2:0 frame (== ffv2amd_ring_send_420) */
+#define FFV2AMD_FRAME_YUV422 8u      /* ffv2amd_codec_send_frame and qpring_send: a 4:2:2 frame (== ffv2amd_ring_send_422);
+                                        with FFV2AMD_FRAME_YUV420 FFV2AMD_ERR_INVAL */
 #define FFV2AMD_FRAME_REGISTER 4u    /* the planes are ordinary (pageable) memory from a pool of long-lived buffers -- what
                                         libavcodec's get_buffer2 hands out: the ring page-locks each distinct buffer the first
                                         time it sees it (hipHostRegister, milliseconds) and lets the DMA engine read it in place
@@ -376,6 +405,11 @@ int   ffv2amd_ring_receive(ffv2amd_encoder *enc, uint8_t *out, size_t out_cap, s
  * stream.  Half the bytes cross PCIe; luma is copied straight into plane 0.  May be mixed with
  * ring_send on one ring.  Parity unpinned. */
 int   ffv2amd_ring_send_420(ffv2amd_encoder *enc, const uint8_t *const data[3], const ptrdiff_t linesize[3],
+                            const int32_t *W, int64_t tag, unsigned flags);
+/* ... and for yuv422p / yuv422p10le / yuv422p12le frames (see ffv2amd_encode_frame_422): two thirds of the
+ * 4:4:4 bytes cross PCIe; luma straight into plane 0, U and V (h rows each) into staging, the chroma
+ * up-conversion on the frame's compute stream.  May be mixed with ring_send and ring_send_420 on one ring. */
+int   ffv2amd_ring_send_422(ffv2amd_encoder *enc, const uint8_t *const data[3], const ptrdiff_t linesize[3],
                             const int32_t *W, int64_t tag, unsigned flags);
 int   ffv2amd_ring_pending(const ffv2amd_encoder *enc);
 void  ffv2amd_ring_close(ffv2amd_encoder *enc);

@@ -76,9 +76,9 @@ int  ffv2amd_codec_close(FFV2AMDCodecContext *avctx);            /* ffv2enc.c:51
 /* avcodec_send_frame / avcodec_receive_packet (encode.c:420,449): asynchronous, up to ring_depth
  * frames in flight per device, FFV2AMD_ERR_AGAIN (= AVERROR(EAGAIN)) when full (receive a packet,
  * then send again) / nothing ready; packets in send order with the frame's pts, whichever device
- * finishes first.  flags: FFV2AMD_FRAME_PINNED, FFV2AMD_FRAME_REGISTER, FFV2AMD_FRAME_YUV420 of ffv2_amd.h (the last:
- * frame->data[0..2] = Y, U, V of a yuv420p* frame of the context's depth, see
- * ffv2amd_codec_encode_yuv420).
+ * finishes first.  flags: FFV2AMD_FRAME_PINNED, FFV2AMD_FRAME_REGISTER, FFV2AMD_FRAME_YUV420 or FFV2AMD_FRAME_YUV422 of
+ * ffv2_amd.h (frame->data[0..2] = Y, U, V of a yuv420p* / yuv422p* frame of the context's depth, see
+ * ffv2amd_codec_encode_yuv420 / _yuv422; both at once is FFV2AMD_ERR_INVAL).
  * global_quality 1..64 goes through ffv2amd_qp_send_frame / _receive_packet: two frames in flight per
  * device, receive_packet always waits (it runs the frame's range coder), a frame the reference
  * would abort on comes back as FFV2AMD_ERR_ABORT.  global_quality must not change while frames
@@ -89,6 +89,10 @@ int  ffv2amd_codec_receive_packet(FFV2AMDCodecContext *avctx, FFV2AMDPacket *avp
  * (fftools/ffmpeg_filter.c:63-131, auto-inserted bicubic scale filter): avctx initialised with the
  * yuv444p* format of the same depth, frame->data[0..2] = Y, U, V.  Parity unpinned. */
 int  ffv2amd_codec_encode_yuv420(FFV2AMDCodecContext *avctx, FFV2AMDPacket *avpkt,
+                                 const FFV2AMDFrame *frame, int *got_packet_ptr);
+/* The same for yuv422p / yuv422p10le / yuv422p12le sources (libavutil/pixdesc.c:2838-2873 picks
+ * yuv444p* of the same depth; libswscale's generic scaler converts).  Parity unpinned. */
+int  ffv2amd_codec_encode_yuv422(FFV2AMDCodecContext *avctx, FFV2AMDPacket *avpkt,
                                  const FFV2AMDFrame *frame, int *got_packet_ptr);
 void ffv2amd_packet_unref(FFV2AMDPacket *pkt);
 
