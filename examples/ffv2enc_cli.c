@@ -13,7 +13,8 @@
  *            yuv420p | yuv420p10le | yuv420p12le and yuv422p | yuv422p10le | yuv422p12le are converted
  *            first, as the ffmpeg tool does (choose_pixel_fmt -> yuv444p* + auto-inserted bicubic scale
  *            filter); --no-convert as a last argument hands them to encode2 unconverted, which refuses
- *            them (exit 2).
+ *            them (exit 2).  So are the semi-planar nv12 | nv21 | p010le | nv16 | nv24 | nv42 (Y, then one
+ *            plane of interleaved chroma pairs: libswscale de-interleaves, P010 >> 6, then the same step).
  * An output name ending in ".mkv" selects the Matroska writer (include/ffv2_amd_mkv.h,
  * "V_FFV2", 25 frames per second) instead of the back-to-back packet stream.
  */
@@ -25,9 +26,21 @@
 #include "ffv2_amd_codec.h"
 #include "ffv2_amd_mkv.h"
 
-/* *sub: 0 for an encoder format, 420 / 422 for a subsampled source converted to the yuv444p* format returned */
-static int parse_fmt(const char *s, int *planes, int *bps, int *sub)
+/* *sub: 0 for an encoder format, 420 / 422 for a subsampled source converted to the yuv444p* format returned;
+   *nv: the FFV2AMD_FRAME_NV* flags of a semi-planar source (*sub 420 / 422 / 444), else 0 */
+static int parse_fmt(const char *s, int *planes, int *bps, int *sub, unsigned *nv)
 {
+    static const struct { const char *n; int id, bps, sub; unsigned flags; } semi[] = {
+        { "nv12", FFV2AMD_PIX_YUV444P, 1, 420, FFV2AMD_FRAME_NV | FFV2AMD_FRAME_YUV420 },
+        { "nv21", FFV2AMD_PIX_YUV444P, 1, 420, FFV2AMD_FRAME_NV | FFV2AMD_FRAME_NV_VU | FFV2AMD_FRAME_YUV420 },
+        { "p010le", FFV2AMD_PIX_YUV444P10LE, 2, 420, FFV2AMD_FRAME_NV | FFV2AMD_FRAME_YUV420 },
+        { "nv16", FFV2AMD_PIX_YUV444P, 1, 422, FFV2AMD_FRAME_NV | FFV2AMD_FRAME_YUV422 },
+        { "nv24", FFV2AMD_PIX_YUV444P, 1, 444, FFV2AMD_FRAME_NV },
+        { "nv42", FFV2AMD_PIX_YUV444P, 1, 444, FFV2AMD_FRAME_NV | FFV2AMD_FRAME_NV_VU },
+    };
+    *nv = 0;
+    for (size_t i = 0; i < sizeof(semi) / sizeof(semi[0]); i++)
+        if (!strcmp(s, semi[i].n)) { *planes = 2; *bps = semi[i].bps; *sub = semi[i].sub; *nv = semi[i].flags; return semi[i].id; }
     static const struct { const char *n; int id, bps, sub; } conv[] = {
         { "yuv420p", FFV2AMD_PIX_YUV444P, 1, 420 }, { "yuv420p10le", FFV2AMD_PIX_YUV444P10LE, 2, 420 },
         { "yuv420p12le", FFV2AMD_PIX_YUV444P12LE, 2, 420 },
@@ -55,10 +68,11 @@ int main(int argc, char **argv)
         return 2;
     }
     int planes = 0, bps = 0, sub = 0;
+    unsigned nv = 0;
     FFV2AMDCodecContext ctx = { 0 };
     ctx.width = atoi(argv[1]);
     ctx.height = atoi(argv[2]);
-    ctx.pix_fmt = parse_fmt(argv[3], &planes, &bps, &sub);
+    ctx.pix_fmt = parse_fmt(argv[3], &planes, &bps, &sub, &nv);
     if (sub && !strcmp(argv[argc - 1], "--no-convert")) {
         fprintf(stderr, "%s is not an encoder input (ffv2enc.c:596-601)\n", argv[3]);
         return 2;
@@ -81,10 +95,11 @@ int main(int argc, char **argv)
     if (ret < 0) { fprintf(stderr, "init failed: %d\n", ret); return 1; }
 
     const size_t plane_bytes = (size_t)ctx.width * ctx.height * bps;
-    const int cw = (ctx.width + 1) / 2, ch = sub == 422 ? ctx.height : (ctx.height + 1) / 2;
+    const int cw = sub == 444 ? ctx.width : (ctx.width + 1) / 2, ch = sub == 420 ? (ctx.height + 1) / 2 : ctx.height;
     const size_t cplane_bytes = (size_t)cw * ch * bps;
+    /* a semi-planar frame: Y, then ch rows of cw interleaved pairs (data[1], 2 * cw samples a row) */
     const size_t frame_bytes = sub ? plane_bytes + 2 * cplane_bytes : plane_bytes * planes;
-    const unsigned sub_flag = sub == 420 ? FFV2AMD_FRAME_YUV420 : sub == 422 ? FFV2AMD_FRAME_YUV422 : 0;
+    const unsigned sub_flag = nv ? nv : sub == 420 ? FFV2AMD_FRAME_YUV420 : sub == 422 ? FFV2AMD_FRAME_YUV422 : 0;
     uint8_t *buf = malloc(frame_bytes);
     if (!buf) return 1;
     long nframes = 0;
@@ -103,7 +118,7 @@ int main(int argc, char **argv)
             if (!have) eof = 1;
             for (int p = 0; p < planes && have; p++) {
                 fr.data[p] = sub ? (p ? buf + plane_bytes + (p - 1) * cplane_bytes : buf) : buf + p * plane_bytes;
-                fr.linesize[p] = (ptrdiff_t)(sub && p ? cw : ctx.width) * bps;
+                fr.linesize[p] = (ptrdiff_t)(sub && p ? (nv ? 2 * cw : cw) : ctx.width) * bps;
             }
             fr.pts = sent;
             for (;;) {
@@ -137,10 +152,11 @@ int main(int argc, char **argv)
         int got = 0;
         for (int p = 0; p < planes; p++) {
             fr.data[p] = sub ? (p ? buf + plane_bytes + (p - 1) * cplane_bytes : buf) : buf + p * plane_bytes;
-            fr.linesize[p] = (ptrdiff_t)(sub && p ? cw : ctx.width) * bps;
+            fr.linesize[p] = (ptrdiff_t)(sub && p ? (nv ? 2 * cw : cw) : ctx.width) * bps;
         }
         fr.pts = nframes;
-        ret = sub == 420 ? ffv2amd_codec_encode_yuv420(&ctx, &pkt, &fr, &got)
+        ret = nv ? ffv2amd_codec_encode_nv(&ctx, &pkt, &fr, nv, &got)
+            : sub == 420 ? ffv2amd_codec_encode_yuv420(&ctx, &pkt, &fr, &got)
             : sub == 422 ? ffv2amd_codec_encode_yuv422(&ctx, &pkt, &fr, &got)
             : ffv2amd_codec_encode2(&ctx, &pkt, &fr, &got);
         if (ret < 0 || !got) { fprintf(stderr, "encode2 failed on frame %ld: %d\n", nframes, ret); break; }

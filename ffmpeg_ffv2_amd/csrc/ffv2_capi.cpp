@@ -387,7 +387,9 @@ void run_parallel(int n, int want, Fn fn)
 }
 
 // What a frame's chroma is when it reaches the device: ready (4:4:4), or waiting for the up-conversion
-enum ChromaKind : uint8_t { CHROMA_444 = 0, CHROMA_420 = 1, CHROMA_422 = 2 };
+// (semi-planar sources: which one, see nv_kind)
+enum ChromaKind : uint8_t { CHROMA_444 = 0, CHROMA_420 = 1, CHROMA_422 = 2,
+                            CHROMA_NV12 = 3, CHROMA_NV21 = 4, CHROMA_P010 = 5, CHROMA_NV16 = 6, CHROMA_NV24 = 7, CHROMA_NV42 = 8 };
 
 // A few persistent host threads that gather the rows of a caller's (pageable) frame into pinned
 // memory, slice by slice, each slice's DMA issued by the thread that gathered it.  The calling
@@ -662,6 +664,7 @@ struct ffv2amd_encoder {
     int32_t *qd_w[2] = { nullptr, nullptr };
     uint8_t *qd_c420[2] = { nullptr, nullptr };          // U, V of a 4:2:0 frame (ffv2amd_qp_send_frame_420)
     uint8_t *qd_c422[2] = { nullptr, nullptr };          // U, V of a 4:2:2 frame (ffv2amd_qp_send_frame_422)
+    uint8_t *qd_cnv[2] = { nullptr, nullptr };           // interleaved chroma of a semi-planar frame (ffv2amd_qp_send_frame_nv)
     int64_t q_tag[2] = { 0, 0 };
     // decoder-side check (ffv2amd_decode_frame)
     int16_t *d_dec_pulses = nullptr;
@@ -679,6 +682,8 @@ struct ffv2amd_encoder {
     FFV2Upconv422 *upconv422 = nullptr;
     bool upconv422_tried = false;
     uint8_t *d_422 = nullptr, *h_422 = nullptr;
+    // semi-planar front end (ffv2amd_*_nv): a tight host frame on its way to the device (encode_frame_nv)
+    uint8_t *d_nv = nullptr, *h_nv = nullptr;
     // asynchronous frame ring (ffv2amd_ring_*)
     struct RingSlot {
         uint8_t  *h_frame = nullptr, *d_frame = nullptr;    // pinned staging frame, device frame
@@ -689,6 +694,7 @@ struct ffv2amd_encoder {
         bool has_w = false;
         uint8_t  *d_c420 = nullptr;                         // U, V of a 4:2:0 frame, rows c_pitch apart (ring_send_420)
         uint8_t  *d_c422 = nullptr;                         // U, V of a 4:2:2 frame, h rows each (ring_send_422)
+        uint8_t  *d_cnv = nullptr;                          // interleaved chroma of a semi-planar frame (ring_send + FRAME_NV)
         hipEvent_t ev_h2d = nullptr, ev_done = nullptr, ev_meta = nullptr;
         int64_t tag = 0;
     };
@@ -758,6 +764,7 @@ struct ffv2amd_encoder {
         uint8_t *d_frames[NBUF] = {};
         uint8_t *d_c420[NBUF] = {};              // 4:2:0 chroma as it arrives: [cap][U plane, V plane]
         uint8_t *d_c422[NBUF] = {};              // 4:2:2 chroma as it arrives: [cap][U plane, V plane]
+        uint8_t *d_cnv[NBUF] = {};               // semi-planar chroma as it arrives: [cap][nv_stage_bytes]
         int32_t *d_w[NBUF] = {};
         bool any_w[NBUF] = {};
         std::vector<int64_t> tags[NBUF];
@@ -880,6 +887,8 @@ void ffv2amd_encoder_destroy(ffv2amd_encoder *e)
     ffv2_upconv422_destroy(e->upconv422);
     (void)hipFree(e->d_422);
     if (e->h_422) (void)hipHostFree(e->h_422);
+    (void)hipFree(e->d_nv);
+    if (e->h_nv) (void)hipHostFree(e->h_nv);
     lanecoder_free(e);
     for (auto &q : e->qset) {
         (void)hipFree(q.d_rec); (void)hipFree(q.d_stream); (void)hipFree(q.d_totals); (void)hipFree(q.d_codes); (void)hipFree(q.d_status);
@@ -896,7 +905,7 @@ void ffv2amd_encoder_destroy(ffv2amd_encoder *e)
     }
     if (e->q_copy) { (void)hipStreamSynchronize(e->q_copy); (void)hipStreamDestroy(e->q_copy); }
     for (int k = 0; k < 2; k++) {
-        (void)hipFree(e->qd_frame[k]); (void)hipFree(e->qd_w[k]); (void)hipFree(e->qd_c420[k]); (void)hipFree(e->qd_c422[k]);
+        (void)hipFree(e->qd_frame[k]); (void)hipFree(e->qd_w[k]); (void)hipFree(e->qd_c420[k]); (void)hipFree(e->qd_c422[k]); (void)hipFree(e->qd_cnv[k]);
         if (e->qh_frame[k]) (void)hipHostFree(e->qh_frame[k]);
     }
     (void)hipFree(e->d_thr); (void)hipFree(e->d_lds_scan); (void)hipFree(e->d_prefix);
@@ -1488,6 +1497,181 @@ int ffv2amd_encode_frame_422(ffv2amd_encoder *e, const uint8_t *const data[3], c
     hipStream_t s = e->stream;
     HIPCHK(hipMemcpyAsync(e->d_422, e->h_422, total, hipMemcpyHostToDevice, s));
     HIPCHK(ffv2_launch_upconv422(e->upconv422, e->geom, 1, e->d_422, total, e->d_frame, s));
+    return encode_uploaded_frame(e, qp, nullptr, out, out_cap, out_size);
+}
+
+// ------------------------------------------------------------------
+// Semi-planar front end: nv12 / nv21 / p010le / nv16 / nv24 / nv42 sources (FFV2AMD_FRAME_NV) -- libswscale's
+// input readers de-interleave (and for P010 shift right by 6), then the 4:2:0 / 4:2:2 paths above run, or
+// for nv24 / nv42 the unscaled de-interleave -- see ffv2_upconv.hip.  PARITY UNPINNED.
+// ------------------------------------------------------------------
+struct NvGeom {
+    size_t bps, y_row, uv_row;     // bytes per sample, per luma row, per interleaved chroma row
+    int ch;                        // chroma rows
+    bool p010;                     // luma needs the shift: the conversion launch writes plane 0 too
+};
+
+// the flags on their own: FFV2AMD_FRAME_NV_VU needs FFV2AMD_FRAME_NV, and one subsampling at most
+static bool nv_flags_ok(unsigned flags)
+{
+    if ((flags & FFV2AMD_FRAME_NV_VU) && !(flags & FFV2AMD_FRAME_NV)) return false;
+    return !((flags & FFV2AMD_FRAME_YUV420) && (flags & FFV2AMD_FRAME_YUV422));
+}
+
+// flags (with FFV2AMD_FRAME_NV) and the encoder's format -> the source format; FFV2AMD_ERR_INVAL for every
+// combination that is not one of the six: 8 bit nv12 nv21 nv16 nv24 nv42, 10 bit p010le
+static int nv_kind(const ffv2amd_info &in, unsigned flags, ChromaKind *kind)
+{
+    if (!(flags & FFV2AMD_FRAME_NV) || !nv_flags_ok(flags)) return FFV2AMD_ERR_INVAL;
+    if (in.planes != 3 || (in.pix_fmt != FFV2AMD_PIX_YUV444P && in.pix_fmt != FFV2AMD_PIX_YUV444P10LE)) return FFV2AMD_ERR_INVAL;
+    const bool vu = (flags & FFV2AMD_FRAME_NV_VU) != 0;
+    if (in.depth == 10) {
+        if (!(flags & FFV2AMD_FRAME_YUV420) || vu) return FFV2AMD_ERR_INVAL;
+        *kind = CHROMA_P010;
+    } else if (flags & FFV2AMD_FRAME_YUV420) {
+        *kind = vu ? CHROMA_NV21 : CHROMA_NV12;
+    } else if (flags & FFV2AMD_FRAME_YUV422) {
+        if (vu) return FFV2AMD_ERR_INVAL;
+        *kind = CHROMA_NV16;
+    } else {
+        *kind = vu ? CHROMA_NV42 : CHROMA_NV24;
+    }
+    return FFV2AMD_OK;
+}
+
+static NvGeom nv_geom(const ffv2amd_info &in, ChromaKind k)
+{
+    NvGeom g;
+    g.bps = in.depth > 8 ? 2 : 1;
+    g.p010 = k == CHROMA_P010;
+    const bool sub420 = k == CHROMA_NV12 || k == CHROMA_NV21 || k == CHROMA_P010;
+    const int cw = k == CHROMA_NV24 || k == CHROMA_NV42 ? in.width : (in.width + 1) >> 1;
+    g.ch = sub420 ? (in.height + 1) >> 1 : in.height;
+    g.y_row = (size_t)in.width * g.bps;
+    g.uv_row = 2 * (size_t)cw * g.bps;
+    return g;
+}
+
+// device staging of one frame's interleaved chroma (rows 128-byte aligned), enough for every kind of the encoder's depth
+static size_t nv_uv_pitch(const NvGeom &g) { return align_up(g.uv_row, 128); }
+static size_t nv_stage_bytes(const ffv2amd_info &in)
+{
+    return align_up(2 * (size_t)in.width * (in.depth > 8 ? 2 : 1), 128) * (size_t)in.height;
+}
+
+// the 4:2:0 / 4:2:2 tables the kind needs
+static int nv_ready(ffv2amd_encoder *e, ChromaKind k)
+{
+    if (k == CHROMA_NV16) return upconv422_ready(e);
+    if (k == CHROMA_NV24 || k == CHROMA_NV42) return FFV2AMD_OK;
+    return upconv_ready(e);
+}
+
+// nframes semi-planar frames of one kind on the device -> the encoder's 4:4:4 frames at dst.  Luma: 8-bit luma is
+// copied, P010 luma shifted by the chroma launch.  d_y == dst (y_pitch = row_pitch, y_frame_stride = frame_stride)
+// means the caller's DMA has put the raw luma into plane 0 already: 8 bit leaves it there, P010 is shifted in place.
+static hipError_t nv_launch(ffv2amd_encoder *e, ChromaKind k, int nframes, const uint8_t *d_y, size_t y_pitch,
+                            size_t y_frame_stride, const uint8_t *d_uv, size_t uv_pitch, size_t uv_frame_stride,
+                            uint8_t *dst, hipStream_t s)
+{
+    const ffv2amd_info &in = e->info;
+    const NvGeom g = nv_geom(in, k);
+    FFV2NvSrc src{ nullptr, y_pitch, y_frame_stride, d_uv, uv_pitch, uv_frame_stride,
+                   k == CHROMA_NV21 || k == CHROMA_NV42, g.p010 ? 6 : 0 };
+    if (g.p010) src.y = d_y;
+    else if (d_y != dst)
+        for (int f = 0; f < nframes; f++) {
+            const hipError_t rc = hipMemcpy2DAsync(dst + (size_t)f * in.frame_stride, in.row_pitch, d_y + (size_t)f * y_frame_stride,
+                                                   y_pitch, g.y_row, (size_t)in.height, hipMemcpyDeviceToDevice, s);
+            if (rc != hipSuccess) return rc;
+        }
+    if (k == CHROMA_NV16) return ffv2_launch_nv422(e->upconv422, e->geom, nframes, src, dst, s);
+    if (k == CHROMA_NV24 || k == CHROMA_NV42) return ffv2_launch_nv444(e->geom, nframes, src, dst, s);
+    return ffv2_launch_nv420(e->upconv, e->geom, nframes, src, dst, s);
+}
+
+size_t ffv2amd_frame_bytes_nv(const ffv2amd_encoder *e, unsigned flags)
+{
+    ChromaKind k;
+    if (!e || nv_kind(e->info, flags, &k) < 0) return 0;
+    const NvGeom g = nv_geom(e->info, k);
+    return g.y_row * (size_t)e->info.height + g.uv_row * (size_t)g.ch;
+}
+
+int ffv2amd_convert_nv_device(ffv2amd_encoder *e, int nframes, const void *d_y, size_t y_pitch, const void *d_uv,
+                              size_t uv_pitch, size_t frame_stride, unsigned flags, void *d_frames444, void *stream)
+{
+    if (!nv_flags_ok(flags) || !(flags & FFV2AMD_FRAME_NV)) return FFV2AMD_ERR_INVAL;
+    if (!e || !d_y || !d_uv || !d_frames444 || nframes < 1) return FFV2AMD_ERR_INVAL;
+    ChromaKind k;
+    int r = nv_kind(e->info, flags, &k);
+    if (r < 0) return r;
+    const NvGeom g = nv_geom(e->info, k);
+    if (y_pitch < g.y_row || uv_pitch < g.uv_row) return FFV2AMD_ERR_INVAL;
+    if (g.bps == 2 && (((uintptr_t)d_y | (uintptr_t)d_uv | y_pitch | uv_pitch | frame_stride) & 1)) return FFV2AMD_ERR_INVAL;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return FFV2AMD_ERR_DEVICE;
+    r = nv_ready(e, k);
+    if (r < 0) return r;
+    HIPCHK(nv_launch(e, k, nframes, (const uint8_t *)d_y, y_pitch, frame_stride, (const uint8_t *)d_uv, uv_pitch, frame_stride,
+                     (uint8_t *)d_frames444, (hipStream_t)stream));
+    return FFV2AMD_OK;
+}
+
+int ffv2amd_debug_nv_time(ffv2amd_encoder *e, int nframes, const void *d_y, size_t y_pitch, const void *d_uv,
+                          size_t uv_pitch, size_t frame_stride, unsigned flags, void *d_frames444, int reps,
+                          float *ms_per_launch)
+{
+    if (!ms_per_launch || reps < 1) return FFV2AMD_ERR_INVAL;
+    int r = ffv2amd_convert_nv_device(e, nframes, d_y, y_pitch, d_uv, uv_pitch, frame_stride, flags, d_frames444, e ? e->stream : nullptr);
+    if (r < 0) return r;                                           // (the warm-up launch)
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return FFV2AMD_ERR_DEVICE;
+    hipStream_t s = e->stream;
+    hipEvent_t a, b;
+    HIPCHK(hipEventCreate(&a));
+    HIPCHK(hipEventCreate(&b));
+    HIPCHK(hipEventRecord(a, s));
+    for (int i = 0; i < reps; i++) {
+        r = ffv2amd_convert_nv_device(e, nframes, d_y, y_pitch, d_uv, uv_pitch, frame_stride, flags, d_frames444, s);
+        if (r < 0) break;
+    }
+    HIPCHK(hipEventRecord(b, s));
+    HIPCHK(hipEventSynchronize(b));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, a, b));
+    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+    if (r < 0) return r;
+    *ms_per_launch = ms / reps;
+    return FFV2AMD_OK;
+}
+
+int ffv2amd_encode_frame_nv(ffv2amd_encoder *e, const uint8_t *const data[2], const ptrdiff_t linesize[2], unsigned flags,
+                            int qp, uint8_t *out, size_t out_cap, size_t *out_size)
+{
+    if (!nv_flags_ok(flags) || !(flags & FFV2AMD_FRAME_NV)) return FFV2AMD_ERR_INVAL;
+    if (!e || !data || !linesize || !out || !out_size || !data[0] || !data[1]) return FFV2AMD_ERR_INVAL;
+    ChromaKind k;
+    int r = nv_kind(e->info, flags, &k);
+    if (r < 0) return r;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return FFV2AMD_ERR_DEVICE;
+    r = nv_ready(e, k);
+    if (r < 0) return r;
+    const ffv2amd_info &in = e->info;
+    const NvGeom g = nv_geom(in, k);
+    if (!e->d_nv) {                                                // the largest tight frame of any kind: 3 planes' worth
+        const size_t cap = 3 * g.y_row * (size_t)in.height;
+        HIPCHK(hipMalloc(&e->d_nv, cap));
+        HIPCHK(hipHostMalloc(&e->h_nv, cap, hipHostMallocDefault));
+    }
+    uint8_t *hy = e->h_nv, *huv = e->h_nv + g.y_row * (size_t)in.height;     // tight rows: Y, then UV
+    for (int y = 0; y < in.height; y++) memcpy(hy + (size_t)y * g.y_row, data[0] + (ptrdiff_t)y * linesize[0], g.y_row);
+    for (int y = 0; y < g.ch; y++) memcpy(huv + (size_t)y * g.uv_row, data[1] + (ptrdiff_t)y * linesize[1], g.uv_row);
+    hipStream_t s = e->stream;
+    const size_t total = g.y_row * (size_t)in.height + g.uv_row * (size_t)g.ch;
+    HIPCHK(hipMemcpyAsync(e->d_nv, e->h_nv, total, hipMemcpyHostToDevice, s));
+    HIPCHK(nv_launch(e, k, 1, e->d_nv, g.y_row, 0, e->d_nv + g.y_row * (size_t)in.height, g.uv_row, 0, e->d_frame, s));
     return encode_uploaded_frame(e, qp, nullptr, out, out_cap, out_size);
 }
 
@@ -2436,6 +2620,46 @@ int ffv2amd_qp_send_frame_422(ffv2amd_encoder *e, const uint8_t *const data[3], 
     return FFV2AMD_OK;
 }
 
+// ... and for a semi-planar frame (data[0] = Y, data[1] = interleaved chroma; flags as for ffv2amd_encode_frame_nv)
+int ffv2amd_qp_send_frame_nv(ffv2amd_encoder *e, const uint8_t *const data[2], const ptrdiff_t linesize[2], unsigned flags,
+                             int qp, int64_t tag)
+{
+    if (!nv_flags_ok(flags) || !(flags & FFV2AMD_FRAME_NV)) return FFV2AMD_ERR_INVAL;
+    if (!e || !data || !linesize || !data[0] || !data[1]) return FFV2AMD_ERR_INVAL;
+    ChromaKind k;
+    int r = nv_kind(e->info, flags, &k);
+    if (r < 0) return r;
+    if (qp < 1 || qp > 64) return FFV2AMD_ERR_UNSUPPORTED;
+    if (e->q_sub - e->q_fin >= 2) return FFV2AMD_ERR_AGAIN;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return FFV2AMD_ERR_DEVICE;
+    r = nv_ready(e, k);
+    if (r < 0) return r;
+    const ffv2amd_info &in = e->info;
+    const NvGeom g = nv_geom(in, k);
+    const int q = (int)(e->q_sub & 1u);
+    const size_t uv_pitch = nv_uv_pitch(g);
+    if (!e->qd_frame[q]) {
+        HIPCHK(hipMalloc(&e->qd_frame[q], in.frame_stride));
+        HIPCHK(hipMalloc(&e->qd_w[q], sizeof(int32_t) * in.block_planes));
+        HIPCHK(hipHostMalloc(&e->qh_frame[q], in.frame_stride, hipHostMallocDefault));
+        memset(e->qh_frame[q], 0, in.frame_stride);
+    }
+    if (!e->qd_cnv[q]) HIPCHK(hipMalloc(&e->qd_cnv[q], nv_stage_bytes(in)));
+    // staging: luma in plane 0 of the page-locked frame, the chroma behind it (ch * uv_pitch <= 2 * h * row_pitch)
+    uint8_t *hy = e->qh_frame[q], *hc = e->qh_frame[q] + in.plane_stride;
+    for (int y = 0; y < in.height; y++) memcpy(hy + (size_t)y * in.row_pitch, data[0] + (ptrdiff_t)y * linesize[0], g.y_row);
+    for (int y = 0; y < g.ch; y++) memcpy(hc + (size_t)y * uv_pitch, data[1] + (ptrdiff_t)y * linesize[1], g.uv_row);
+    hipStream_t s = e->stream;
+    HIPCHK(hipMemcpyAsync(e->qd_frame[q], hy, in.row_pitch * (size_t)in.height, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(e->qd_cnv[q], hc, uv_pitch * (size_t)g.ch, hipMemcpyHostToDevice, s));
+    HIPCHK(nv_launch(e, k, 1, e->qd_frame[q], in.row_pitch, 0, e->qd_cnv[q], uv_pitch, 0, e->qd_frame[q], s));
+    r = ffv2amd_qp_submit(e, 1, e->qd_frame[q], qp, nullptr);
+    if (r < 0) return r;
+    e->q_tag[q] = tag;
+    return FFV2AMD_OK;
+}
+
 int ffv2amd_qp_receive_packet(ffv2amd_encoder *e, uint8_t *out, size_t out_cap, size_t *out_size, int64_t *tag)
 {
     if (!e || !out || !out_size) return FFV2AMD_ERR_INVAL;
@@ -2472,8 +2696,9 @@ int ffv2amd_qpring_close(ffv2amd_encoder *e)
     (void)hipStreamSynchronize(e->stream);
     (void)ffv2amd_lanecoder_close(e);
     for (int i = 0; i < ffv2amd_encoder::QpRing::NBUF; i++) {
-        (void)hipFree(r.d_frames[i]); (void)hipFree(r.d_c420[i]); (void)hipFree(r.d_c422[i]); (void)hipFree(r.d_w[i]);
-        r.d_frames[i] = nullptr; r.d_c420[i] = nullptr; r.d_c422[i] = nullptr; r.d_w[i] = nullptr; r.any_w[i] = false; r.tags[i].clear();
+        (void)hipFree(r.d_frames[i]); (void)hipFree(r.d_c420[i]); (void)hipFree(r.d_c422[i]); (void)hipFree(r.d_cnv[i]); (void)hipFree(r.d_w[i]);
+        r.d_frames[i] = nullptr; r.d_c420[i] = nullptr; r.d_c422[i] = nullptr; r.d_cnv[i] = nullptr; r.d_w[i] = nullptr;
+        r.any_w[i] = false; r.tags[i].clear();
     }
     for (int i = 0; i < ffv2amd_encoder::QpRing::NBOUNCE; i++) {
         if (r.bounce[i]) (void)hipHostFree(r.bounce[i]);
@@ -2611,7 +2836,7 @@ static int qpring_submit(ffv2amd_encoder *e)
     HIPCHK(hipEventRecord(r.ev_batch, r.h2d));
     HIPCHK(hipStreamWaitEvent(e->stream, r.ev_batch, 0));
     const int b = r.fill;
-    {   // 4:2:0 and 4:2:2 frames of the batch: their chroma is up-converted now, one launch per run of frames of one
+    {   // 4:2:0, 4:2:2 and semi-planar frames of the batch: their chroma is converted now, one launch per run of frames of one
         // kind (a launch per frame on the copy stream stood in the queue behind the coder's long kernels every other run)
         const ffv2amd_info &in = e->info;
         const size_t bps = in.depth > 8 ? 2 : 1;
@@ -2626,7 +2851,12 @@ static int qpring_submit(ffv2amd_encoder *e)
             if (kind == CHROMA_420)
                 HIPCHK(ffv2_launch_upconv_chroma(e->upconv, e->geom, i1 - i0, r.d_c420[b] + (size_t)i0 * c_frame, c_pitch,
                                                  c_pitch * (size_t)ch, c_frame, r.d_frames[b] + (size_t)i0 * in.frame_stride, e->stream));
-            else
+            else if (kind != CHROMA_422) {     // semi-planar: luma in plane 0 already (P010: shifted there in place)
+                uint8_t *d0 = r.d_frames[b] + (size_t)i0 * in.frame_stride;
+                const size_t st = nv_stage_bytes(in);
+                HIPCHK(nv_launch(e, (ChromaKind)kind, i1 - i0, d0, in.row_pitch, in.frame_stride, r.d_cnv[b] + (size_t)i0 * st,
+                                 nv_uv_pitch(nv_geom(in, (ChromaKind)kind)), st, d0, e->stream));
+            } else
                 HIPCHK(ffv2_launch_upconv422_chroma(e->upconv422, e->geom, i1 - i0, r.d_c422[b] + (size_t)i0 * c_frame422, c_pitch,
                                                     c_pitch * (size_t)in.height, c_frame422,
                                                     r.d_frames[b] + (size_t)i0 * in.frame_stride, e->stream));
@@ -2656,8 +2886,14 @@ int ffv2amd_qpring_send(ffv2amd_encoder *e, const uint8_t *const data[4], const 
     const ffv2amd_info &in = e->info;
     const bool is420 = (flags & FFV2AMD_FRAME_YUV420) != 0, is422 = (flags & FFV2AMD_FRAME_YUV422) != 0;
     if (is420 && is422) return FFV2AMD_ERR_INVAL;
-    const bool sub = is420 || is422;                             // chroma goes to staging, luma into plane 0
-    const int npl = sub ? 3 : in.planes;
+    const bool nv = (flags & (FFV2AMD_FRAME_NV | FFV2AMD_FRAME_NV_VU)) != 0;    // data = Y, interleaved chroma
+    ChromaKind nvk = CHROMA_444;
+    if (nv) {
+        const int rc = nv_kind(in, flags, &nvk);
+        if (rc < 0) return rc;
+    }
+    const bool sub = (is420 || is422) && !nv;                    // chroma goes to staging, luma into plane 0
+    const int npl = nv ? 2 : sub ? 3 : in.planes;
     if (sub && in.planes != 3) return FFV2AMD_ERR_INVAL;
     for (int p = 0; p < npl; p++)
         if (!data[p]) return FFV2AMD_ERR_INVAL;
@@ -2681,6 +2917,11 @@ int ffv2amd_qpring_send(ffv2amd_encoder *e, const uint8_t *const data[4], const 
         if (rc < 0) return rc;
         if (!r.d_c422[b]) HIPCHK(hipMalloc(&r.d_c422[b], 2 * c_pitch * (size_t)ch * (size_t)r.cap));
     }
+    if (nv) {
+        int rc = nv_ready(e, nvk);
+        if (rc < 0) return rc;
+        if (!r.d_cnv[b]) HIPCHK(hipMalloc(&r.d_cnv[b], nv_stage_bytes(in) * (size_t)r.cap));
+    }
     uint8_t *d_frame = r.d_frames[b] + (size_t)r.count * in.frame_stride;
     uint8_t *d_c = sub ? (is422 ? r.d_c422[b] : r.d_c420[b]) + (size_t)r.count * 2 * c_pitch * (size_t)ch : nullptr;
     // where each plane goes: rows `pitch` apart on the device
@@ -2692,6 +2933,11 @@ int ffv2amd_qpring_send(ffv2amd_encoder *e, const uint8_t *const data[4], const 
         pl[p].pitch = chroma ? c_pitch : in.row_pitch;
         pl[p].rows = chroma ? ch : in.height;
         pl[p].dst = chroma ? d_c + (size_t)(p - 1) * c_pitch * (size_t)ch : d_frame + (size_t)(sub ? 0 : p) * in.plane_stride;
+    }
+    if (nv) {
+        const NvGeom g = nv_geom(in, nvk);
+        pl[0] = Pl{ data[0], linesize[0], g.y_row, in.row_pitch, in.height, d_frame };
+        pl[1] = Pl{ data[1], linesize[1], g.uv_row, nv_uv_pitch(g), g.ch, r.d_cnv[b] + (size_t)r.count * nv_stage_bytes(in) };
     }
     hipStream_t sh = r.h2d;
     bool in_place = (flags & FFV2AMD_FRAME_PINNED) != 0;
@@ -2752,7 +2998,7 @@ int ffv2amd_qpring_send(ffv2amd_encoder *e, const uint8_t *const data[4], const 
         }
         HIPCHK(hipEventRecord(r.ev_bounce[k], sh));
     }
-    r.chroma[b][(size_t)r.count] = is420 ? CHROMA_420 : is422 ? CHROMA_422 : CHROMA_444;   // up-converted when the batch leaves (qpring_submit)
+    r.chroma[b][(size_t)r.count] = nv ? nvk : is420 ? CHROMA_420 : is422 ? CHROMA_422 : CHROMA_444;   // converted when the batch leaves (qpring_submit)
     if (W) {
         if (!r.d_w[b]) HIPCHK(hipMalloc(&r.d_w[b], sizeof(int32_t) * nb * (size_t)r.cap));
         if (!r.any_w[b]) {
@@ -2937,7 +3183,7 @@ void ffv2amd_ring_close(ffv2amd_encoder *e)
         if (st) (void)hipStreamSynchronize(st);
     for (auto &r : e->ring) {
         (void)hipFree(r.d_frame); (void)hipFree(r.d_pkt); (void)hipFree(r.d_meta);
-        (void)hipFree(r.d_codes); (void)hipFree(r.d_bitcnt); (void)hipFree(r.d_w); (void)hipFree(r.d_c420); (void)hipFree(r.d_c422);
+        (void)hipFree(r.d_codes); (void)hipFree(r.d_bitcnt); (void)hipFree(r.d_w); (void)hipFree(r.d_c420); (void)hipFree(r.d_c422); (void)hipFree(r.d_cnv);
         if (r.h_frame) (void)hipHostFree(r.h_frame);
         if (r.h_pkt) (void)hipHostFree(r.h_pkt);
         if (r.h_meta) (void)hipHostFree(r.h_meta);
@@ -3035,7 +3281,7 @@ struct RingPlane {
     uint8_t *d_dst, *stage;
 };
 
-// H2D of the planes, then T-stage + E-stage on a compute stream (4:2:0, 4:2:2: the chroma up-conversion in
+// H2D of the planes, then T-stage + E-stage on a compute stream (4:2:0, 4:2:2, semi-planar: the chroma conversion in
 // front of them), then the {size, status} D2H: the body of ring_send / ring_send_420 / ring_send_422.
 static int ring_submit(ffv2amd_encoder *e, ffv2amd_encoder::RingSlot &r, const RingPlane *pl, int npl, ChromaKind chroma,
                        const int32_t *W, int64_t tag, unsigned flags)
@@ -3118,6 +3364,8 @@ static int ring_submit(ffv2amd_encoder *e, ffv2amd_encoder::RingSlot &r, const R
     else if (chroma == CHROMA_422)
         HIPCHK(ffv2_launch_upconv422_chroma(e->upconv422, e->geom, 1, r.d_c422, pl[1].pitch, pl[1].pitch * (size_t)pl[1].rows, 0,
                                             r.d_frame, sc));
+    else if (chroma != CHROMA_444)             // semi-planar: luma is in plane 0 already (P010: shifted there in place)
+        HIPCHK(nv_launch(e, chroma, 1, r.d_frame, in.row_pitch, 0, r.d_cnv, pl[1].pitch, 0, r.d_frame, sc));
     int rc = launch_encode_qp0(e, 1, r.d_frame, dW, r.d_pkt, in.packet_cap, r.d_meta, (int32_t *)(r.d_meta + 1),
                                r.d_codes, r.d_bitcnt, nullptr, sc, sc, nullptr, (int32_t *)(r.d_meta + 2));
     if (rc < 0) return rc;
@@ -3130,10 +3378,39 @@ static int ring_submit(ffv2amd_encoder *e, ffv2amd_encoder::RingSlot &r, const R
     return FFV2AMD_OK;
 }
 
+// a semi-planar frame through the ring: data[0] = Y straight into plane 0 of the slot, data[1] = the interleaved
+// chroma into a staging area, the conversion on the frame's compute stream (ffv2_upconv.hip)
+static int ring_send_nv(ffv2amd_encoder *e, const uint8_t *const data[4], const ptrdiff_t linesize[4],
+                        const int32_t *W, int64_t tag, unsigned flags)
+{
+    const ffv2amd_info &in = e->info;
+    ChromaKind k;
+    int rc = nv_kind(in, flags, &k);
+    if (rc < 0) return rc;
+    if (!data[0] || !data[1]) return FFV2AMD_ERR_INVAL;
+    if (e->ring_count == (int)e->ring.size()) return FFV2AMD_ERR_AGAIN;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return FFV2AMD_ERR_DEVICE;
+    rc = nv_ready(e, k);
+    if (rc < 0) return rc;
+    const NvGeom g = nv_geom(in, k);
+    auto &r = e->ring[(size_t)((e->ring_head + e->ring_count) % (int)e->ring.size())];
+    if (!r.d_cnv) HIPCHK(hipMalloc(&r.d_cnv, nv_stage_bytes(in)));
+    // pinned staging of a pageable frame: luma in plane 0 of the slot's host frame, the chroma behind it
+    // (ch * uv_pitch <= 2 * h * row_pitch: it fits planes 1 and 2)
+    const size_t uv_pitch = nv_uv_pitch(g);
+    RingPlane pl[2] = {
+        RingPlane{ data[0], linesize[0], g.y_row, in.row_pitch, in.height, 4, r.d_frame, r.h_frame },
+        RingPlane{ data[1], linesize[1], g.uv_row, uv_pitch, g.ch, g.ch == in.height ? 4 : 2, r.d_cnv, r.h_frame + in.plane_stride },
+    };
+    return ring_submit(e, r, pl, 2, k, W, tag, flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_REGISTER));
+}
+
 int ffv2amd_ring_send(ffv2amd_encoder *e, const uint8_t *const data[4], const ptrdiff_t linesize[4],
                       const int32_t *W, int64_t tag, unsigned flags)
 {
     if (!e || !data || !linesize || e->ring.empty()) return FFV2AMD_ERR_INVAL;
+    if (flags & (FFV2AMD_FRAME_NV | FFV2AMD_FRAME_NV_VU)) return ring_send_nv(e, data, linesize, W, tag, flags);
     const ffv2amd_info &in = e->info;
     for (int p = 0; p < in.planes; p++)
         if (!data[p]) return FFV2AMD_ERR_INVAL;

@@ -97,6 +97,23 @@ hipError_t ffv2_launch_upconv422(const FFV2Upconv422 *u, const FFV2Geom &g, int 
 hipError_t ffv2_launch_upconv422_chroma(const FFV2Upconv422 *u, const FFV2Geom &g, int nframes, const uint8_t *src_u,
                                         size_t c_pitch, size_t c_plane_stride, size_t src_frame_stride, uint8_t *dst,
                                         hipStream_t s);
+// semi-planar sources -> 4:4:4 (ffv2_upconv.hip): nv12 / nv21 / p010le through the 4:2:0 tables, nv16 through the
+// 4:2:2 table, nv24 / nv42 de-interleaved.  Planes 1 and 2 of dst are written; plane 0 too where y is set (4:2:0 only).
+struct FFV2NvSrc {
+    const uint8_t *y;          // frame 0's luma, rows y_pitch apart, shifted into plane 0 by this launch; nullptr: not
+    size_t y_pitch;            // this launch's business (a copy).  May be plane 0 of dst itself (y_pitch = row_pitch).
+    size_t y_frame_stride;     // frame f's luma at y + f * y_frame_stride
+    const uint8_t *uv;         // frame 0's interleaved chroma, rows uv_pitch apart
+    size_t uv_pitch;
+    size_t frame_stride;       // frame f's uv at + f * frame_stride
+    bool vu;                   // V first (nv21, nv42)
+    int shift;                 // every sample >> shift as it is read (p010le: 6)
+};
+hipError_t ffv2_launch_nv420(const FFV2Upconv *u, const FFV2Geom &g, int nframes, const FFV2NvSrc &src, uint8_t *dst,
+                             hipStream_t s);
+hipError_t ffv2_launch_nv422(const FFV2Upconv422 *u, const FFV2Geom &g, int nframes, const FFV2NvSrc &src, uint8_t *dst,
+                             hipStream_t s);
+hipError_t ffv2_launch_nv444(const FFV2Geom &g, int nframes, const FFV2NvSrc &src, uint8_t *dst, hipStream_t s);
 
 // qp > 0 entropy coder on the device (ffv2_rangecoder.hip): one wavefront per frame
 struct FFV2RangeCoderArgs {

@@ -163,13 +163,66 @@ struct UpArgs {
     const int32_t *hp, *vp;
 };
 
-template <int BPS>
-__global__ __launch_bounds__(256) void ffv2_upconv_kernel(const UpArgs a)
+// Where a source's chroma samples are: two planes, or one plane of interleaved pairs (NV12 & co.: U first,
+// NV21 & co.: V first).  The kernels below are written once for all three; LAY_PLANAR compiles to what it
+// did before the semi-planar front end existed.
+enum SrcLayout { LAY_PLANAR = 0, LAY_UV = 1, LAY_VU = 2 };
+
+// the semi-planar front end's extra arguments: src is the interleaved plane (c_plane_stride 0), every sample
+// is shifted right by `shift` as it is read (P010: 6); with ysrc the same launch also writes plane 0 from
+// that luma (frame f at + f * y_frame_stride, rows y_pitch apart), shifted the same way
+struct UpArgsNv : UpArgs {
+    const uint8_t *ysrc;
+    size_t y_pitch, y_frame_stride;
+    int shift;
+};
+
+template <int L> struct UpArgsOf { using type = UpArgsNv; };
+template <> struct UpArgsOf<LAY_PLANAR> { using type = UpArgs; };
+
+// which interleaved component plane p (1 = U, 2 = V) is
+template <int L> __device__ __forceinline__ int comp_of(int p) { return L == LAY_VU ? 2 - p : p - 1; }
+
+template <int L, typename A> __device__ __forceinline__ int shift_of(const A &a)
+{
+    if constexpr (L == LAY_PLANAR) return 0;
+    else return a.shift;
+}
+
+// chroma sample i of a row of one plane (planar) or of component `comp` (interleaved)
+template <int BPS, int L>
+__device__ __forceinline__ int c_sample(const uint8_t *row, int i, int comp, int shift)
+{
+    if constexpr (L == LAY_PLANAR) {
+        return BPS == 1 ? row[i] : reinterpret_cast<const uint16_t *>(row)[i];
+    } else {
+        const int j = 2 * i + comp;
+        return (BPS == 1 ? row[j] : reinterpret_cast<const uint16_t *>(row)[j]) >> shift;
+    }
+}
+
+template <int BPS, int L = LAY_PLANAR>
+__global__ __launch_bounds__(256) void ffv2_upconv_kernel(const typename UpArgsOf<L>::type a)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    const int p = 1 + (int)(blockIdx.z & 1u), f = (int)(blockIdx.z >> 1);
+    int p = 1 + (int)(blockIdx.z & 1u), f = (int)(blockIdx.z >> 1);
+    if constexpr (L != LAY_PLANAR) {
+        if (a.ysrc) {                          // luma blocks in the same grid: z = 3 * frame + plane
+            p = (int)(blockIdx.z % 3u); f = (int)(blockIdx.z / 3u);
+            if (p == 0) {
+                if (x >= a.w) return;
+                const uint8_t *row = a.ysrc + (size_t)f * a.y_frame_stride + (size_t)y * a.y_pitch;
+                const int v = (BPS == 1 ? row[x] : reinterpret_cast<const uint16_t *>(row)[x]) >> a.shift;
+                uint8_t *dp = a.dst + (size_t)f * a.frame_stride + (size_t)y * a.row_pitch;
+                if (BPS == 1) dp[x] = (uint8_t)v;
+                else reinterpret_cast<uint16_t *>(dp)[x] = (uint16_t)v;
+                return;
+            }
+        }
+    }
     if (x >= a.w) return;
     const uint8_t *sp = a.src + (size_t)f * a.src_frame_stride + (size_t)(p - 1) * a.c_plane_stride;
+    const int comp = comp_of<L>(p), csh = shift_of<L>(a);
     const int hp = a.hp[x], vp = a.vp[y];
     int hc[UP_TAPS], vc[UP_TAPS];
 #pragma unroll
@@ -181,7 +234,7 @@ __global__ __launch_bounds__(256) void ffv2_upconv_kernel(const UpArgs a)
         const uint8_t *row = sp + (size_t)(vp + j) * a.c_pitch;
         int hv = 0;
         for (int k = 0; k < a.htaps; k++) {
-            const int s = BPS == 1 ? row[hp + k] : reinterpret_cast<const uint16_t *>(row)[hp + k];
+            const int s = c_sample<BPS, L>(row, hp + k, comp, csh);
             hv += s * hc[k];
         }
         hv >>= hsh;
@@ -201,8 +254,50 @@ constexpr int UT_W = 128, UT_H = 32;           // output tile
 constexpr int UT_SR = 24, UT_SC = 80;          // source patch bound (rows, columns); checked on the host per geometry
 constexpr int UT_HP = UT_W + 8;                // int16 per row of the horizontal-pass buffer (272 B rows)
 
+// plane 0 of one output tile from a semi-planar source's luma: 8 samples per item, shifted right by a.shift.
+// In place (ysrc = plane 0 of dst, y_pitch = row_pitch) is fine: every item reads the vector it writes.
 template <int BPS>
-__global__ __launch_bounds__(256) void ffv2_upconv_tile_kernel(const UpArgs a)
+__device__ __forceinline__ void nv_luma_tile(const UpArgsNv &a, int f, int x0, int y0, int t)
+{
+    const uint8_t *ys = a.ysrc + (size_t)f * a.y_frame_stride;
+    uint8_t *yd = a.dst + (size_t)f * a.frame_stride;
+#pragma unroll
+    for (int it = 0; it < UT_W * UT_H / 8 / 256; it++) {
+        const int id = t + 256 * it;
+        const int y = y0 + (id >> 4), x = x0 + (id & 15) * 8;
+        if (y >= a.h || x >= a.w) continue;
+        const uint8_t *sr = ys + (size_t)y * a.y_pitch + (size_t)x * BPS;
+        uint32_t v[8];
+        if (x + 8 <= a.w && ((uintptr_t)sr & (8 * BPS - 1)) == 0) {
+            if constexpr (BPS == 1) {
+                const uint2 q = *reinterpret_cast<const uint2 *>(sr);
+#pragma unroll
+                for (int e = 0; e < 4; e++) { v[e] = (q.x >> (8 * e)) & 0xffu; v[4 + e] = (q.y >> (8 * e)) & 0xffu; }
+            } else {
+                const uint4 q = *reinterpret_cast<const uint4 *>(sr);
+                const uint32_t w[4] = { q.x, q.y, q.z, q.w };
+#pragma unroll
+                for (int e = 0; e < 4; e++) { v[2 * e] = w[e] & 0xffffu; v[2 * e + 1] = w[e] >> 16; }
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; e++)
+                v[e] = x + e < a.w ? (BPS == 1 ? sr[e] : reinterpret_cast<const uint16_t *>(sr)[e]) : 0u;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; e++) v[e] >>= a.shift;
+        // the row pitch is a multiple of 128 bytes: a whole vector may be written past the picture's last sample
+        uint8_t *dp = yd + (size_t)y * a.row_pitch + (size_t)x * BPS;
+        if constexpr (BPS == 1)
+            *reinterpret_cast<uint2 *>(dp) = make_uint2(v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24),
+                                                        v[4] | (v[5] << 8) | (v[6] << 16) | (v[7] << 24));
+        else
+            *reinterpret_cast<uint4 *>(dp) = make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
+    }
+}
+
+template <int BPS, int L = LAY_PLANAR>
+__global__ __launch_bounds__(256) void ffv2_upconv_tile_kernel(const typename UpArgsOf<L>::type a)
 {
     __shared__ uint16_t patch[UT_SR][UT_SC];
     __shared__ __attribute__((aligned(16))) int16_t hbuf[UT_SR][UT_HP];
@@ -210,8 +305,15 @@ __global__ __launch_bounds__(256) void ffv2_upconv_tile_kernel(const UpArgs a)
     __shared__ int vps[UT_H];
     const int t = threadIdx.x;
     const int x0 = blockIdx.x * UT_W, y0 = blockIdx.y * UT_H;
-    const int p = 1 + (int)(blockIdx.z & 1u), f = (int)(blockIdx.z >> 1);
+    int p = 1 + (int)(blockIdx.z & 1u), f = (int)(blockIdx.z >> 1);
+    if constexpr (L != LAY_PLANAR) {
+        if (a.ysrc) {                          // luma tiles in the same grid: z = 3 * frame + plane
+            p = (int)(blockIdx.z % 3u); f = (int)(blockIdx.z / 3u);
+            if (p == 0) { nv_luma_tile<BPS>(a, f, x0, y0, t); return; }
+        }
+    }
     const uint8_t *sp = a.src + (size_t)f * a.src_frame_stride + (size_t)(p - 1) * a.c_plane_stride;
+    const int comp = comp_of<L>(p), csh = shift_of<L>(a);
     const int xl = min(x0 + UT_W, a.w) - 1, yl = min(y0 + UT_H, a.h) - 1;     // last output column / row of the tile
     const int cs0 = a.hp[x0], cs1 = min(a.hp[xl] + a.htaps, a.cw);           // source columns [cs0, cs1)
     const int rs0 = a.vp[y0], rs1 = min(a.vp[yl] + a.vtaps, a.ch);
@@ -221,7 +323,7 @@ __global__ __launch_bounds__(256) void ffv2_upconv_tile_kernel(const UpArgs a)
         const int r = i / UT_SC, c = i - r * UT_SC;
         if (c < ncols) {
             const uint8_t *row = sp + (size_t)(rs0 + r) * a.c_pitch;
-            patch[r][c] = BPS == 1 ? row[cs0 + c] : reinterpret_cast<const uint16_t *>(row)[cs0 + c];
+            patch[r][c] = (uint16_t)c_sample<BPS, L>(row, cs0 + c, comp, csh);
         }
     }
     if (t < UT_H) {
@@ -465,18 +567,21 @@ __device__ __forceinline__ int u2_out(int hv, int depth)
     return v < 0 ? 0 : (v > hi ? hi : v);
 }
 
-template <int BPS>
+// interleaved (NV16) sources: src is the UV plane (c_plane_stride 0), component by comp_of<L>, no shift
+template <int BPS, int L = LAY_PLANAR>
 __global__ __launch_bounds__(256) void ffv2_upconv422_kernel(const Up422Args a)
 {
     using S = U2Shape<BPS>;
     constexpr int VEC = S::VEC, TW = S::TW, SPAN = S::SPAN, RW = S::RW;
+    constexpr int PAIR = L == LAY_PLANAR ? 1 : 2;       // samples per source column
     __shared__ uint16_t span[4][RW][SPAN];     // [wave][row]
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int x0 = blockIdx.x * TW, yw = blockIdx.y * S::ROWS + wv * RW;    // the wave's rows: yw .. yw + RW - 1
     const int p = 1 + (int)(blockIdx.z & 1u), f = (int)(blockIdx.z >> 1);
+    const int comp = comp_of<L>(p);
     const int xl = min(x0 + TW, a.w) - 1;
     const int s0 = a.hp[x0], ns = min(a.hp[xl] + a.htaps, a.cw) - s0;      // source columns [s0, s0 + ns)
-    const uint8_t *sp = a.src + (size_t)f * a.src_frame_stride + (size_t)(p - 1) * a.c_plane_stride + (size_t)s0 * BPS;
+    const uint8_t *sp = a.src + (size_t)f * a.src_frame_stride + (size_t)(p - 1) * a.c_plane_stride + (size_t)s0 * BPS * PAIR;
     // the source spans of the wave's rows -> LDS, four rows at a time: the loads are unconditional (indices clamped
     // into the span and the picture) so that all of them are in flight before the first is waited for
 #pragma unroll
@@ -488,7 +593,7 @@ __global__ __launch_bounds__(256) void ffv2_upconv422_kernel(const Up422Args a)
 #pragma unroll
             for (int k = 0; k < S::LOADS; k++) {
                 const int i = min(lane + 64 * k, ns - 1);
-                v[j][k] = BPS == 1 ? row[i] : reinterpret_cast<const uint16_t *>(row)[i];
+                v[j][k] = (uint32_t)c_sample<BPS, L>(row, i, comp, 0);
             }
         }
 #pragma unroll
@@ -540,7 +645,7 @@ __global__ __launch_bounds__(256) void ffv2_upconv422_kernel(const Up422Args a)
 }
 
 // one thread per output sample, any tap count up to UP_TAPS, taps read from global memory
-template <int BPS>
+template <int BPS, int L = LAY_PLANAR>
 __global__ __launch_bounds__(256) void ffv2_upconv422_naive_kernel(const Up422Args a)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
@@ -550,7 +655,7 @@ __global__ __launch_bounds__(256) void ffv2_upconv422_naive_kernel(const Up422Ar
     const int hp = a.hp[x];
     int hv = 0;
     for (int k = 0; k < a.htaps; k++) {
-        const int s = BPS == 1 ? row[hp + k] : reinterpret_cast<const uint16_t *>(row)[hp + k];
+        const int s = c_sample<BPS, L>(row, hp + k, comp_of<L>(p), 0);
         hv += s * a.hf[(size_t)x * UP_TAPS + k];
     }
     const int v = u2_out<BPS>(hv >> (BPS == 1 ? 7 : a.depth - 1), a.depth);
@@ -661,4 +766,136 @@ hipError_t ffv2_launch_upconv422(const FFV2Upconv422 *u, const FFV2Geom &g, int 
     const size_t cw = (size_t)((g.width + 1) >> 1);
     return ffv2_launch_upconv422_chroma(u, g, nframes, src + (size_t)g.width * g.height * bps, cw * bps, cw * g.height * bps,
                                         src_frame_stride, dst, s);
+}
+
+// =============================================================================================
+// Semi-planar sources: one plane of interleaved chroma pairs instead of two planes.
+//   nv12 / nv21 / p010le   4:2:0, 8 / 8 / 10 bit;  nv16  4:2:2, 8 bit;  nv24 / nv42  4:4:4, 8 bit.
+// What the reference tool chain makes of them before encode2() (ffv2enc.c:596-601 lists yuv444p* only):
+//   format   av_find_best_pix_fmt_of_2 / get_pix_fmt_score (libavutil/pixdesc.c:2838-2873) picks the
+//            yuv444p* format of the same component depth: the loss flags of a deeper or a subsampled
+//            candidate cost more, and P010's depth is 10 (pixdesc.c:2102-2113), so yuv444p10le;
+//   input    libswscale's input readers only de-interleave (nvXXtoUV_c, libswscale/input.c:686-698);
+//            P010's also shift every sample right by 6, dropping the low 6 bits (p010LEToY_c /
+//            p010LEToUV_c, input.c:700-726), and the scaler then runs at c->srcBpc = 10
+//            (libswscale/utils.c:1416-1418);
+//   4:2:0 / 4:2:2  the generic scaler follows on those planes exactly as for yuv420p* / yuv422p*: the
+//            4:2:0 and 4:2:2 paths above, reading the interleaved plane (ffv2_upconv_tile_kernel /
+//            ffv2_upconv_kernel / ffv2_upconv422_kernel / ffv2_upconv422_naive_kernel with L = LAY_UV,
+//            LAY_VU);
+//   4:4:4    ff_get_unscaled_swscale has an exact converter for nv24 / nv42 -> yuv444p
+//            (nv24ToPlanarWrapper, libswscale/swscale_unscaled.c:1926-1930): a pure de-interleave,
+//            ffv2_nv444_kernel.
+// PARITY UNPINNED, as for the planar front ends: no libswscale binary or vector exists here.
+//
+// Device part: sources are pitched (decoder surfaces are padded): luma pitch, chroma pitch and frame
+// stride are separate.  A 4:2:0 / 4:2:2 workgroup reads its component of the pairs straight from
+// the interleaved rows (every other sample).  P010 luma needs the shift, so the 4:2:0 launch carries
+// luma tiles in the same grid (z = 3 * frame + plane) -- also in place, where the ring's DMA has put
+// the raw samples into plane 0 already; 8-bit luma is a plain copy (DMA).
+// =============================================================================================
+namespace {
+
+struct Nv444Args {
+    const uint8_t *uv;         // frame 0's interleaved plane, rows uv_pitch apart, frame f at + f * src_frame_stride
+    size_t uv_pitch, src_frame_stride;
+    uint8_t *dst;
+    size_t frame_stride, plane_stride, row_pitch;
+    int w, h;
+};
+
+// 8-bit nv24 / nv42 -> planes 1 and 2: a lane takes 8 pairs (one 16-byte load where the row allows it)
+// and writes 8 samples to each plane; a wave takes 512 columns of one row, a workgroup 4 rows
+template <int L>
+__global__ __launch_bounds__(256) void ffv2_nv444_kernel(const Nv444Args a)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int x = (blockIdx.x * 64 + lane) * 8, y = blockIdx.y * 4 + wv, f = blockIdx.z;
+    if (x >= a.w || y >= a.h) return;
+    const uint8_t *s = a.uv + (size_t)f * a.src_frame_stride + (size_t)y * a.uv_pitch + (size_t)x * 2;
+    uint32_t w[4];
+    if (x + 8 <= a.w && ((uintptr_t)s & 15) == 0) {
+        const uint4 q = *reinterpret_cast<const uint4 *>(s);
+        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            w[i] = 0;
+#pragma unroll
+            for (int b = 0; b < 4; b++)
+                if (x + 2 * i + (b >> 1) < a.w) w[i] |= (uint32_t)s[4 * i + b] << (8 * b);
+        }
+    }
+    // bytes 0, 2 of each dword are the first component, 1, 3 the second (v_perm_b32 material)
+    const uint32_t c0lo = (w[0] & 0xffu) | ((w[0] >> 8) & 0xff00u) | ((w[1] << 16) & 0xff0000u) | ((w[1] << 8) & 0xff000000u);
+    const uint32_t c0hi = (w[2] & 0xffu) | ((w[2] >> 8) & 0xff00u) | ((w[3] << 16) & 0xff0000u) | ((w[3] << 8) & 0xff000000u);
+    const uint32_t c1lo = ((w[0] >> 8) & 0xffu) | ((w[0] >> 16) & 0xff00u) | ((w[1] << 8) & 0xff0000u) | (w[1] & 0xff000000u);
+    const uint32_t c1hi = ((w[2] >> 8) & 0xffu) | ((w[2] >> 16) & 0xff00u) | ((w[3] << 8) & 0xff0000u) | (w[3] & 0xff000000u);
+    // the row pitch is a multiple of 128 bytes: the 8 samples may run past the picture's last one
+    uint8_t *d = a.dst + (size_t)f * a.frame_stride + (size_t)y * a.row_pitch + x;
+    uint8_t *du = d + a.plane_stride, *dv = d + 2 * a.plane_stride;
+    *reinterpret_cast<uint2 *>(L == LAY_VU ? dv : du) = make_uint2(c0lo, c0hi);
+    *reinterpret_cast<uint2 *>(L == LAY_VU ? du : dv) = make_uint2(c1lo, c1hi);
+}
+
+}  // namespace
+
+hipError_t ffv2_launch_nv420(const FFV2Upconv *u, const FFV2Geom &g, int nframes, const FFV2NvSrc &src, uint8_t *dst,
+                             hipStream_t s)
+{
+    const int bps = g.bytes_per_sample;
+    UpArgsNv a{};
+    a.src = src.uv; a.dst = dst; a.src_frame_stride = src.frame_stride; a.c_plane_stride = 0; a.c_pitch = src.uv_pitch;
+    a.frame_stride = g.frame_stride; a.plane_stride = g.plane_stride; a.row_pitch = g.row_pitch;
+    a.w = g.width; a.h = g.height; a.cw = (g.width + 1) >> 1; a.ch = (g.height + 1) >> 1; a.depth = g.depth;
+    a.htaps = u->htaps; a.vtaps = u->vtaps; a.hf = u->d_hf; a.vf = u->d_vf; a.hp = u->d_hp; a.vp = u->d_vp;
+    a.ysrc = src.y; a.y_pitch = src.y_pitch; a.y_frame_stride = src.y_frame_stride; a.shift = src.shift;
+    const unsigned nz = (unsigned)((src.y ? 3 : 2) * nframes);
+    static const int force_naive = getenv("FFV2AMD_UPCONV_NAIVE") ? atoi(getenv("FFV2AMD_UPCONV_NAIVE")) : 0;
+#define NV_LAUNCH(K, grid)                                                                                      \
+    do {                                                                                                        \
+        if (bps == 1 && !src.vu) hipLaunchKernelGGL((K<1, LAY_UV>), grid, dim3(256), 0, s, a);                  \
+        else if (bps == 1)       hipLaunchKernelGGL((K<1, LAY_VU>), grid, dim3(256), 0, s, a);                  \
+        else                     hipLaunchKernelGGL((K<2, LAY_UV>), grid, dim3(256), 0, s, a);                  \
+    } while (0)
+    if (bps == 2 && src.vu) return hipErrorInvalidValue;       // no 16-bit V-first 4:2:0 source is accepted
+    if (u->tiled && !force_naive)
+        NV_LAUNCH(ffv2_upconv_tile_kernel, dim3((unsigned)((g.width + UT_W - 1) / UT_W), (unsigned)((g.height + UT_H - 1) / UT_H), nz));
+    else
+        NV_LAUNCH(ffv2_upconv_kernel, dim3((unsigned)((g.width + 255) / 256), (unsigned)g.height, nz));
+#undef NV_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t ffv2_launch_nv422(const FFV2Upconv422 *u, const FFV2Geom &g, int nframes, const FFV2NvSrc &src, uint8_t *dst,
+                             hipStream_t s)
+{
+    if (g.bytes_per_sample != 1 || src.vu || src.y || src.shift) return hipErrorInvalidValue;     // nv16 only
+    Up422Args a{};
+    a.src = src.uv; a.dst = dst; a.src_frame_stride = src.frame_stride; a.c_plane_stride = 0; a.c_pitch = src.uv_pitch;
+    a.frame_stride = g.frame_stride; a.plane_stride = g.plane_stride; a.row_pitch = g.row_pitch;
+    a.w = g.width; a.h = g.height; a.cw = (g.width + 1) >> 1; a.depth = g.depth;
+    a.htaps = u->htaps; a.hf = u->d_hf; a.hp = u->d_hp;
+    if (ffv2_upconv422_uses_strips(u)) {
+        const dim3 grid((unsigned)((g.width + U2Shape<1>::TW - 1) / U2Shape<1>::TW),
+                        (unsigned)((g.height + U2Shape<1>::ROWS - 1) / U2Shape<1>::ROWS), (unsigned)(2 * nframes));
+        hipLaunchKernelGGL((ffv2_upconv422_kernel<1, LAY_UV>), grid, dim3(256), 0, s, a);
+    } else {
+        const dim3 grid((unsigned)((g.width + 255) / 256), (unsigned)g.height, (unsigned)(2 * nframes));
+        hipLaunchKernelGGL((ffv2_upconv422_naive_kernel<1, LAY_UV>), grid, dim3(256), 0, s, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t ffv2_launch_nv444(const FFV2Geom &g, int nframes, const FFV2NvSrc &src, uint8_t *dst, hipStream_t s)
+{
+    if (g.bytes_per_sample != 1 || src.y || src.shift) return hipErrorInvalidValue;               // nv24 / nv42 only
+    Nv444Args a{};
+    a.uv = src.uv; a.uv_pitch = src.uv_pitch; a.src_frame_stride = src.frame_stride; a.dst = dst;
+    a.frame_stride = g.frame_stride; a.plane_stride = g.plane_stride; a.row_pitch = g.row_pitch;
+    a.w = g.width; a.h = g.height;
+    const dim3 grid((unsigned)((g.width + 511) / 512), (unsigned)((g.height + 3) / 4), (unsigned)nframes), block(256);
+    if (src.vu) hipLaunchKernelGGL(ffv2_nv444_kernel<LAY_VU>, grid, block, 0, s, a);
+    else        hipLaunchKernelGGL(ffv2_nv444_kernel<LAY_UV>, grid, block, 0, s, a);
+    return hipGetLastError();
 }

@@ -209,6 +209,34 @@ int ffv2amd_codec_encode_yuv422(FFV2AMDCodecContext *avctx, FFV2AMDPacket *avpkt
     return 0;
 }
 
+/* The same for a semi-planar source (nv12 / nv21 / p010le / nv16 / nv24 / nv42: frame->data[0] = Y,
+ * frame->data[1] = interleaved chroma; flags = FFV2AMD_FRAME_NV | ..., see ffv2amd_frame_bytes_nv):
+ * av_find_best_pix_fmt_of_2 (libavutil/pixdesc.c:2838-2873) selects yuv444p* of the same depth,
+ * libswscale de-interleaves (input.c:686-726) and converts, then encode2() runs.  PARITY UNPINNED. */
+int ffv2amd_codec_encode_nv(FFV2AMDCodecContext *avctx, FFV2AMDPacket *avpkt,
+                            const FFV2AMDFrame *frame, unsigned flags, int *got_packet_ptr)
+{
+    FFV2AMDEncCtx *s;
+    size_t n = 0;
+    int ret;
+    if (!avctx || !avctx->priv_data || !avpkt || !frame || !got_packet_ptr)
+        return FFV2AMD_ERR_INVAL;
+    s = avctx->priv_data;
+    *got_packet_ptr = 0;
+    if (avctx->global_quality > 0 && s->scratch_cap < s->info.packet_cap_qp)
+        return FFV2AMD_ERR_NOSPACE;
+    ret = ffv2amd_encode_frame_nv(s->enc, (const uint8_t *const *)frame->data, frame->linesize,
+                                  flags & (FFV2AMD_FRAME_NV | FFV2AMD_FRAME_NV_VU | FFV2AMD_FRAME_YUV420 | FFV2AMD_FRAME_YUV422),
+                                  avctx->global_quality, s->scratch, s->scratch_cap, &n);
+    if (ret < 0)
+        return ret;
+    ret = hand_over(s, avpkt, n, frame->pts);
+    if (ret < 0)
+        return ret;
+    *got_packet_ptr = 1;
+    return 0;
+}
+
 /* avcodec_send_frame / avcodec_receive_packet (encode.c:420,449): the caller is ONE thread feeding
  * frames and collecting packets; frames are independent (ffv2enc.c:461-469), so frame n goes to
  * device n % ndev -- each device has its own encoder and asynchronous ring (global_quality 0) or
@@ -218,11 +246,17 @@ int ffv2amd_codec_send_frame(FFV2AMDCodecContext *avctx, const FFV2AMDFrame *fra
     FFV2AMDEncCtx *s;
     ffv2amd_encoder *enc;
     const int qp = avctx ? avctx->global_quality : 0;
+    unsigned nv;                                /* a semi-planar frame: its FFV2AMD_FRAME_NV* and subsampling flags */
     int ret, mode;
     if (!avctx || !avctx->priv_data || qp < 0)
         return FFV2AMD_ERR_INVAL;
     if ((flags & FFV2AMD_FRAME_YUV420) && (flags & FFV2AMD_FRAME_YUV422))
         return FFV2AMD_ERR_INVAL;
+    if ((flags & FFV2AMD_FRAME_NV_VU) && !(flags & FFV2AMD_FRAME_NV))
+        return FFV2AMD_ERR_INVAL;
+    nv = flags & (FFV2AMD_FRAME_NV | FFV2AMD_FRAME_NV_VU | FFV2AMD_FRAME_YUV420 | FFV2AMD_FRAME_YUV422);
+    if (!(flags & FFV2AMD_FRAME_NV))
+        nv = 0;
     s = avctx->priv_data;
     if (!frame) {                               /* end of stream: batches that are not full yet go out */
         if (s->mode == 3)
@@ -251,9 +285,12 @@ int ffv2amd_codec_send_frame(FFV2AMDCodecContext *avctx, const FFV2AMDFrame *fra
             s->qpring_qp = qp;
         }
         ret = ffv2amd_qpring_send(enc, frame->data, frame->linesize, NULL, frame->pts,
-                                  flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_YUV420 | FFV2AMD_FRAME_YUV422 | FFV2AMD_FRAME_REGISTER));
+                                  flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_YUV420 | FFV2AMD_FRAME_YUV422 | FFV2AMD_FRAME_REGISTER |
+                                           FFV2AMD_FRAME_NV | FFV2AMD_FRAME_NV_VU));
     } else if (mode == 2) {
-        ret = flags & FFV2AMD_FRAME_YUV420
+        ret = nv
+            ? ffv2amd_qp_send_frame_nv(enc, (const uint8_t *const *)frame->data, frame->linesize, nv, qp, frame->pts)
+            : flags & FFV2AMD_FRAME_YUV420
             ? ffv2amd_qp_send_frame_420(enc, frame->data, frame->linesize, qp, frame->pts)
             : flags & FFV2AMD_FRAME_YUV422
             ? ffv2amd_qp_send_frame_422(enc, frame->data, frame->linesize, qp, frame->pts)
@@ -268,7 +305,9 @@ int ffv2amd_codec_send_frame(FFV2AMDCodecContext *avctx, const FFV2AMDFrame *fra
                 }
             s->ring_open = 1;
         }
-        ret = flags & FFV2AMD_FRAME_YUV420
+        ret = nv
+            ? ffv2amd_ring_send(enc, frame->data, frame->linesize, NULL, frame->pts, nv | (flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_REGISTER)))
+            : flags & FFV2AMD_FRAME_YUV420
             ? ffv2amd_ring_send_420(enc, frame->data, frame->linesize, NULL, frame->pts, flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_REGISTER))
             : flags & FFV2AMD_FRAME_YUV422
             ? ffv2amd_ring_send_422(enc, frame->data, frame->linesize, NULL, frame->pts, flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_REGISTER))

@@ -16,6 +16,14 @@ PIX_FMTS = {  # allowed_pix_fmts, ffv2enc.c:596-601 (AVPixelFormat values of the
     "gbrp": 73, "gbrp10le": 77, "gbrp12le": 137,
 }
 
+# semi-planar source formats -> (FFV2AMD_FRAME_NV* | subsampling flags, the depth of the encoder they go with)
+FRAME_YUV420, FRAME_YUV422, FRAME_NV, FRAME_NV_VU = 2, 8, 16, 32
+NV_FORMATS = {
+    "nv12": (FRAME_NV | FRAME_YUV420, 8), "nv21": (FRAME_NV | FRAME_NV_VU | FRAME_YUV420, 8),
+    "p010le": (FRAME_NV | FRAME_YUV420, 10), "nv16": (FRAME_NV | FRAME_YUV422, 8),
+    "nv24": (FRAME_NV, 8), "nv42": (FRAME_NV | FRAME_NV_VU, 8),
+}
+
 
 class FFV2Encoder:
     def __init__(self, width, height, pix_fmt="yuv444p", device=0, max_batch=1):
@@ -246,6 +254,73 @@ class FFV2Encoder:
         _lib.check(self._lib.ffv2amd_upconvert_422_device(self._h, 1, src.data_ptr(), dst.data_ptr(), C.c_void_p(stream)),
                    "ffv2amd_upconvert_422_device")
         return self.unpack_frames(dst.cpu().numpy())[0]
+
+    # -- semi-planar front end (nv12 nv21 p010le nv16 nv24 nv42: Y plane + one plane of interleaved chroma pairs) --
+    def nv_flags(self, fmt):
+        """FFV2AMD_FRAME_NV* flags of a semi-planar format name; FFV2Error(-22) for a name this encoder does not take
+        (8-bit formats need a yuv444p encoder, p010le a yuv444p10le one)."""
+        if fmt not in NV_FORMATS or NV_FORMATS[fmt][1] != self.info.depth or self.info.planes != 3:
+            raise _lib.FFV2Error(-22, "semi-planar format %s for a %d-bit encoder" % (fmt, self.info.depth))
+        return NV_FORMATS[fmt][0]
+
+    def nv_shape(self, fmt):
+        """((H, W), (chroma rows, 2 * chroma columns)): the sample shapes of a frame's Y and interleaved chroma."""
+        i = self.info
+        f = self.nv_flags(fmt)
+        cw = i.width if not f & (FRAME_YUV420 | FRAME_YUV422) else (i.width + 1) // 2
+        ch = (i.height + 1) // 2 if f & FRAME_YUV420 else i.height
+        return (i.height, i.width), (ch, 2 * cw)
+
+    def _nv_host(self, y, uv, fmt, copy=True):
+        ys, cs = self.nv_shape(fmt)
+        if copy:
+            y = np.ascontiguousarray(y, self.dtype); uv = np.ascontiguousarray(uv, self.dtype)
+        uv = uv.reshape(uv.shape[0], -1) if uv.ndim == 3 else uv
+        for a, shp in ((y, ys), (uv, cs)):
+            assert a.dtype == self.dtype and a.shape == shp and a.strides[1] == self.dtype.itemsize, (a.dtype, a.shape, shp)
+        data = (C.c_void_p * 4)(y.ctypes.data, uv.ctypes.data, None, None)
+        ls = (C.c_ssize_t * 4)(y.strides[0], uv.strides[0], 0, 0)
+        return (y, uv), data, ls                                   # the arrays: the pointers live as long as they do
+
+    def frame_bytes_nv(self, fmt):
+        return self._lib.ffv2amd_frame_bytes_nv(self._h, self.nv_flags(fmt))
+
+    def encode2_nv(self, y, uv, fmt, qp=0):
+        """Semi-planar host frame (Y (H,W); chroma (rows, 2 * columns), pairs interleaved) -> packet bytes."""
+        flags = self.nv_flags(fmt)
+        keep, data, ls = self._nv_host(y, uv, fmt)
+        out = np.empty(self.info.packet_cap if qp == 0 else self.info.packet_cap_qp, np.uint8)
+        n = C.c_size_t(0)
+        _lib.check(self._lib.ffv2amd_encode_frame_nv(self._h, data, ls, flags, qp, out.ctypes.data_as(C.c_void_p), out.size,
+                                                     C.byref(n)), "ffv2amd_encode_frame_nv")
+        del keep
+        return out[: n.value].tobytes()
+
+    def convert_nv(self, y, uv, fmt, out=None, stream=None):
+        """Semi-planar frames resident on the device -> the (F, frame_stride) uint8 4:4:4 batch for
+        encode_batch_device, asynchronously on `stream` (default: torch's current stream).  y: (H, W) or (F, H, W),
+        uv: (rows, 2 * columns) or (F, rows, 2 * columns) torch tensors of 8- or 16-bit samples (p010le: uint16 or
+        int16), unit stride along a row; rows and frames may be strided views into a larger allocation (decoder
+        surfaces): the pitches come from the row strides, and y and uv must have the same frame stride in bytes."""
+        import torch
+        flags = self.nv_flags(fmt)
+        ys, cs = self.nv_shape(fmt)
+        if y.dim() == 2:
+            y, uv = y.unsqueeze(0), uv.unsqueeze(0)
+        F = y.shape[0]
+        isz = self.dtype.itemsize
+        assert y.element_size() == isz and uv.element_size() == isz, (y.dtype, uv.dtype)
+        assert tuple(y.shape[1:]) == ys and tuple(uv.shape[1:]) == cs and uv.shape[0] == F, (tuple(y.shape), tuple(uv.shape), ys, cs)
+        assert y.stride(2) == 1 and uv.stride(2) == 1 and y.device == uv.device
+        assert F == 1 or y.stride(0) == uv.stride(0), "y and uv need one frame stride"
+        if out is None:
+            out = torch.empty((F, self.info.frame_stride), dtype=torch.uint8, device=y.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(y.device).cuda_stream
+        _lib.check(self._lib.ffv2amd_convert_nv_device(
+            self._h, F, y.data_ptr(), y.stride(1) * isz, uv.data_ptr(), uv.stride(1) * isz, y.stride(0) * isz if F > 1 else 0,
+            flags, out.data_ptr(), C.c_void_p(stream)), "ffv2amd_convert_nv_device")
+        return out
 
     def set_device_coder(self, on=True):
         """qp > 0: run the adaptive range coder on the device (one wavefront per frame) instead of host threads."""
@@ -548,6 +623,32 @@ class FFV2Encoder:
             out.append((yy, uu, vv))
         return out
 
+    def ring_send_nv(self, y, uv, fmt, tag=0, pinned=False, register=False):
+        """A semi-planar frame through the ring (Y (H,W); interleaved chroma (rows, 2 * columns), any row stride):
+        converted on the frame's compute stream.  False when the ring is full."""
+        flags = self.nv_flags(fmt)
+        _, data, ls = self._nv_host(y, uv, fmt, copy=False)
+        r = self._lib.ffv2amd_ring_send(self._h, data, ls, None, int(tag), flags | (1 if pinned else 0) | (4 if register else 0))
+        if r == -11:
+            return False
+        _lib.check(r, "ring_send(nv)")
+        return True
+
+    def pinned_frames_nv(self, count, fmt):
+        """count page-locked semi-planar frames as a list of (Y, chroma) sample arrays, for ring_send_nv(pinned=True).
+        Free with free_pinned()."""
+        ys, cs = self.nv_shape(fmt)
+        bps = self.dtype.itemsize
+        yb, cb = ys[0] * ys[1] * bps, cs[0] * cs[1] * bps
+        per = (yb + cb + 127) // 128 * 128
+        ptr = self._lib.ffv2amd_host_alloc(count * per)
+        if not ptr:
+            raise MemoryError("ffv2amd_host_alloc(%d)" % (count * per))
+        self._pinned = getattr(self, "_pinned", []) + [ptr]
+        buf = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * per,))
+        return [(buf[n * per: n * per + yb].view(self.dtype).reshape(ys), buf[n * per + yb: n * per + yb + cb].view(self.dtype).reshape(cs))
+                for n in range(count)]
+
     def ring_receive(self, wait=True):
         """-> (tag, packet bytes) of the oldest frame in flight, or None (nothing in flight /
         wait=False and not finished yet).  A failed frame raises FFV2Error."""
@@ -566,11 +667,12 @@ class FFV2Encoder:
         cap = packet_cap or self.info.packet_cap_qp
         self._qpring_out = np.empty(int(cap) + 16, np.uint8)
 
-    def qpring_send(self, frame, tag=0, W=None, pinned=False, yuv420=False, register=False, yuv422=False):
+    def qpring_send(self, frame, tag=0, W=None, pinned=False, yuv420=False, register=False, yuv422=False, nv=None):
         """frame: (P,H,W) host array, or with yuv420=True / yuv422=True the (Y, U, V) arrays of a yuv420p* / yuv422p*
-        frame.  False: EAGAIN (receive packets first, then send the frame again)."""
+        frame, or with nv="nv12" (any name of NV_FORMATS) the (Y, interleaved chroma) arrays of a semi-planar frame.
+        False: EAGAIN (receive packets first, then send the frame again)."""
         i = self.info
-        planes = list(frame) if yuv420 or yuv422 else [frame[p] for p in range(i.planes)]
+        planes = list(frame) if yuv420 or yuv422 or nv else [frame[p] for p in range(i.planes)]
         data = (C.c_void_p * 4)()
         ls = (C.c_ssize_t * 4)()
         for p, a in enumerate(planes):
@@ -584,7 +686,7 @@ class FFV2Encoder:
             wp = W.ctypes.data_as(C.c_void_p)
         r = self._lib.ffv2amd_qpring_send(self._h, data, ls, wp, int(tag),
                                           (1 if pinned else 0) | (2 if yuv420 else 0) | (4 if register else 0) |
-                                          (8 if yuv422 else 0))
+                                          (8 if yuv422 else 0) | (self.nv_flags(nv) if nv else 0))
         if r == -11:
             return False
         _lib.check(r, "qpring_send")

@@ -175,6 +175,40 @@ int  ffv2amd_upconvert_422_device(ffv2amd_encoder *enc, int nframes, const void 
 int  ffv2amd_encode_frame_422(ffv2amd_encoder *enc, const uint8_t *const data[3], const ptrdiff_t linesize[3],
                               int qp, uint8_t *out, size_t out_cap, size_t *out_size);
 
+/* Semi-planar front end: sources whose chroma is one plane of interleaved pairs, as hardware decoders hand them
+ * over.  flags = FFV2AMD_FRAME_NV, plus FFV2AMD_FRAME_YUV420 / FFV2AMD_FRAME_YUV422 for the subsampling (neither:
+ * 4:4:4), plus FFV2AMD_FRAME_NV_VU for V first; the encoder's depth picks the sample layout:
+ *     yuv444p encoder      nv12 (NV|YUV420)  nv21 (NV|NV_VU|YUV420)  nv16 (NV|YUV422)  nv24 (NV)  nv42 (NV|NV_VU)
+ *     yuv444p10le encoder  p010le (NV|YUV420): 16-bit little-endian samples, the 10 bits in the high bits
+ * Every other combination (yuv444p12le, gbrp*, NV_VU without NV, YUV420 with YUV422, ...) is FFV2AMD_ERR_INVAL,
+ * returned before a device is touched.  What the reference tool chain makes of these sources:
+ * av_find_best_pix_fmt_of_2 / get_pix_fmt_score (libavutil/pixdesc.c:2838-2873) over ffv2enc.c:596-601 pick
+ * yuv444p* of the same component depth (P010's is 10: pixdesc.c:2102-2113); libswscale's input readers
+ * de-interleave (nvXXtoUV_c, libswscale/input.c:686-698) and for P010 shift every sample right by 6
+ * (p010LEToY_c / p010LEToUV_c, input.c:700-726), then the generic scaler runs the yuv420p* / yuv422p* path above at
+ * the source depth (c->srcBpc, libswscale/utils.c:1416-1418); nv24 / nv42 -> yuv444p is the exact unscaled
+ * de-interleave (nv24ToPlanarWrapper, libswscale/swscale_unscaled.c:1926-1930).  PARITY UNPINNED (no libswscale
+ * binary or vector here).
+ *   frame_bytes_nv     : bytes of a tightly packed frame (Y rows, then the chroma rows); 0 for a NULL encoder or
+ *                        bad flags.
+ *   convert_nv_device  : nframes pitched device surfaces -> the encoder's 4:4:4 frame layout (d_frames444, ready
+ *                        for encode_batch_device / lanecoder_submit), on `stream`.  Frame f's luma is at
+ *                        d_y + f * frame_stride (rows y_pitch bytes apart), its chroma at d_uv + f * frame_stride
+ *                        (rows uv_pitch apart); pitches of at least one row, even for p010le.
+ *   encode_frame_nv    : one host frame (data[0] = Y, data[1] = chroma, with their own linesizes) -> packet, any qp.
+ *   qp_send_frame_nv   : the same frame into the qp > 0 pipeline (see ffv2amd_qp_send_frame_420).
+ * ffv2amd_ring_send and ffv2amd_qpring_send take such frames too (data[0] = Y, data[1] = chroma): luma straight into
+ * plane 0, the chroma into staging, the conversion on the frame's compute stream. */
+#define FFV2AMD_FRAME_NV    16u
+#define FFV2AMD_FRAME_NV_VU 32u
+size_t ffv2amd_frame_bytes_nv(const ffv2amd_encoder *enc, unsigned flags);
+int  ffv2amd_convert_nv_device(ffv2amd_encoder *enc, int nframes, const void *d_y, size_t y_pitch, const void *d_uv,
+                               size_t uv_pitch, size_t frame_stride, unsigned flags, void *d_frames444, void *stream);
+int  ffv2amd_encode_frame_nv(ffv2amd_encoder *enc, const uint8_t *const data[2], const ptrdiff_t linesize[2], unsigned flags,
+                             int qp, uint8_t *out, size_t out_cap, size_t *out_size);
+int  ffv2amd_qp_send_frame_nv(ffv2amd_encoder *enc, const uint8_t *const data[2], const ptrdiff_t linesize[2], unsigned flags,
+                              int qp, int64_t tag);
+
 /* The same batch step for 1 <= qp <= 64 split in two, so that consecutive batches overlap:
  *   qp_submit : T-stage, PVQ search and symbol compaction of one batch, asynchronous on the
  *               encoder's stream (frames must be complete when it is called); at most two
@@ -224,7 +258,8 @@ int  ffv2amd_qp_pending(const ffv2amd_encoder *enc);
  *                    been received: the DMA engine reads them in place), FFV2AMD_FRAME_REGISTER (the same promise for
  *                    ordinary memory from a pool of long-lived buffers, page-locked here on first sight) and/or
  *                    FFV2AMD_FRAME_YUV420 (data = Y, U, V of a yuv420p* frame) or FFV2AMD_FRAME_YUV422 (of a
- *                    yuv422p* frame; both at once is FFV2AMD_ERR_INVAL) -- one batch may mix the three; otherwise the rows are copied before
+ *                    yuv422p* frame; both at once is FFV2AMD_ERR_INVAL), or FFV2AMD_FRAME_NV (data = Y, chroma of a
+ *                    semi-planar frame, see ffv2amd_frame_bytes_nv) -- one batch may mix them all; otherwise the rows are copied before
  *                    the call returns (into about 256 MB of page-locked bounce frames the ring owns, by helper
  *                    threads as in ring_send: FFV2AMD_GATHER_THREADS).
  *                    FFV2AMD_ERR_AGAIN: a batch is full, two calls are in flight and the packets of the one
@@ -312,6 +347,11 @@ int    ffv2amd_debug_pvq_time(ffv2amd_encoder *enc, int nframes, const void *d_f
  * average ms per launch over `reps` launches (tools/bench_422.py). */
 int    ffv2amd_debug_upconv422_time(ffv2amd_encoder *enc, int nframes, const void *d_src422, void *d_frames444, int reps,
                                     float *ms_per_launch);
+/* Benchmark aid: ffv2amd_convert_nv_device (luma included) on the encoder's stream after one warm-up launch: average ms
+ * per launch over `reps` launches (tools/bench_nv.py). */
+int    ffv2amd_debug_nv_time(ffv2amd_encoder *enc, int nframes, const void *d_y, size_t y_pitch, const void *d_uv,
+                             size_t uv_pitch, size_t frame_stride, unsigned flags, void *d_frames444, int reps,
+                             float *ms_per_launch);
 int    ffv2amd_lanecoder_encode(ffv2amd_encoder *enc, int nframes, const void *d_frames, int qp,
                                 const int32_t *d_W, uint8_t *h_packets, size_t packet_stride,
                                 uint32_t *h_sizes, int32_t *h_status);
@@ -371,6 +411,8 @@ int  ffv2amd_encoder_flush(ffv2amd_encoder *enc, void *stream);
  * HIP stream.  One thread drives a ring; packets come back in send order with the tag given at
  * send.  encode2() itself stays one-in/one-out (the reference sets no AV_CODEC_CAP_DELAY).
  *   ring_send    : FFV2AMD_ERR_AGAIN when `depth` frames are in flight (receive one first).
+ *                  flags & FFV2AMD_FRAME_NV: data[0] = Y, data[1] = interleaved chroma of a semi-planar frame
+ *                  (see ffv2amd_frame_bytes_nv), converted on the device in front of the T-stage.
  *                  flags & FFV2AMD_FRAME_PINNED: the planes are page-locked (ffv2amd_host_alloc,
  *                  hipHostMalloc/hipHostRegister) and stay untouched until the frame's packet has
  *                  been received -- the DMA engine then reads them in place (planes that follow
@@ -384,7 +426,8 @@ int  ffv2amd_encoder_flush(ffv2amd_encoder *enc, void *stream);
  *                  Copies back the packet's own size, not the capacity.  A frame that fails
  *                  (status < 0) is dropped from the ring and its error returned. */
 #define FFV2AMD_FRAME_PINNED 1u
-#define FFV2AMD_FRAME_YUV420 2u      /* ffv2amd_codec_send_frame only: a 4:2:0 frame (== ffv2amd_ring_send_420) */
+#define FFV2AMD_FRAME_YUV420 2u      /* ffv2amd_codec_send_frame only: a 4:2:0 frame (== ffv2amd_ring_send_420); with
+                                        FFV2AMD_FRAME_NV (ring_send too): the chroma subsampling of a semi-planar frame */
 #define FFV2AMD_FRAME_YUV422 8u      /* ffv2amd_codec_send_frame and qpring_send: a 4:2:2 frame (== ffv2amd_ring_send_422);
                                         with FFV2AMD_FRAME_YUV420 FFV2AMD_ERR_INVAL */
 #define FFV2AMD_FRAME_REGISTER 4u    /* the planes are ordinary (pageable) memory from a pool of long-lived buffers -- what

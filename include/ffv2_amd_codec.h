@@ -78,7 +78,8 @@ int  ffv2amd_codec_close(FFV2AMDCodecContext *avctx);            /* ffv2enc.c:51
  * then send again) / nothing ready; packets in send order with the frame's pts, whichever device
  * finishes first.  flags: FFV2AMD_FRAME_PINNED, FFV2AMD_FRAME_REGISTER, FFV2AMD_FRAME_YUV420 or FFV2AMD_FRAME_YUV422 of
  * ffv2_amd.h (frame->data[0..2] = Y, U, V of a yuv420p* / yuv422p* frame of the context's depth, see
- * ffv2amd_codec_encode_yuv420 / _yuv422; both at once is FFV2AMD_ERR_INVAL).
+ * ffv2amd_codec_encode_yuv420 / _yuv422; both at once is FFV2AMD_ERR_INVAL), or FFV2AMD_FRAME_NV with FFV2AMD_FRAME_NV_VU
+ * and the subsampling flags (frame->data[0..1] = Y, interleaved chroma of a semi-planar frame, see ffv2amd_codec_encode_nv).
  * global_quality 1..64 goes through ffv2amd_qp_send_frame / _receive_packet: two frames in flight per
  * device, receive_packet always waits (it runs the frame's range coder), a frame the reference
  * would abort on comes back as FFV2AMD_ERR_ABORT.  global_quality must not change while frames
@@ -94,6 +95,11 @@ int  ffv2amd_codec_encode_yuv420(FFV2AMDCodecContext *avctx, FFV2AMDPacket *avpk
  * yuv444p* of the same depth; libswscale's generic scaler converts).  Parity unpinned. */
 int  ffv2amd_codec_encode_yuv422(FFV2AMDCodecContext *avctx, FFV2AMDPacket *avpkt,
                                  const FFV2AMDFrame *frame, int *got_packet_ptr);
+/* ... and for semi-planar sources: frame->data[0] = Y, frame->data[1] = interleaved chroma; flags FFV2AMD_FRAME_NV
+ * (| FFV2AMD_FRAME_NV_VU | FFV2AMD_FRAME_YUV420 / _YUV422) pick nv12 / nv21 / p010le / nv16 / nv24 / nv42 as in
+ * ffv2_amd.h (ffv2amd_frame_bytes_nv).  Parity unpinned. */
+int  ffv2amd_codec_encode_nv(FFV2AMDCodecContext *avctx, FFV2AMDPacket *avpkt,
+                             const FFV2AMDFrame *frame, unsigned flags, int *got_packet_ptr);
 void ffv2amd_packet_unref(FFV2AMDPacket *pkt);
 
 #ifdef __cplusplus
