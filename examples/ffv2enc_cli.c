@@ -14,7 +14,10 @@
  *            first, as the ffmpeg tool does (choose_pixel_fmt -> yuv444p* + auto-inserted bicubic scale
  *            filter); --no-convert as a last argument hands them to encode2 unconverted, which refuses
  *            them (exit 2).  So are the semi-planar nv12 | nv21 | p010le | nv16 | nv24 | nv42 (Y, then one
- *            plane of interleaved chroma pairs: libswscale de-interleaves, P010 >> 6, then the same step).
+ *            plane of interleaved chroma pairs: libswscale de-interleaves, P010 >> 6, then the same step),
+ *            and the packed RGB rgb24 | bgr24 | argb | rgba | abgr | bgra | 0rgb | rgb0 | 0bgr | bgr0 (into gbrp)
+ *            and rgb48le | rgb48be | bgr48le | bgr48be | rgba64le | rgba64be | bgra64le | bgra64be (into
+ *            gbrp12le), converted by libswscale's exact unscaled converters (alpha and padding bytes dropped).
  * An output name ending in ".mkv" selects the Matroska writer (include/ffv2_amd_mkv.h,
  * "V_FFV2", 25 frames per second) instead of the back-to-back packet stream.
  */
@@ -27,9 +30,25 @@
 #include "ffv2_amd_mkv.h"
 
 /* *sub: 0 for an encoder format, 420 / 422 for a subsampled source converted to the yuv444p* format returned;
-   *nv: the FFV2AMD_FRAME_NV* flags of a semi-planar source (*sub 420 / 422 / 444), else 0 */
-static int parse_fmt(const char *s, int *planes, int *bps, int *sub, unsigned *nv)
+   *nv: the FFV2AMD_FRAME_NV* flags of a semi-planar source (*sub 420 / 422 / 444), else 0;
+   *pk: the FFV2AMD_PIX_* value of a packed RGB source converted to the gbrp* format returned (*planes: its
+   components per pixel), else 0 */
+static int parse_fmt(const char *s, int *planes, int *bps, int *sub, unsigned *nv, int *pk)
 {
+    static const struct { const char *n; int src, id, bps, nc; } packed[] = {
+        { "rgb24", FFV2AMD_PIX_RGB24, FFV2AMD_PIX_GBRP, 1, 3 },     { "bgr24", FFV2AMD_PIX_BGR24, FFV2AMD_PIX_GBRP, 1, 3 },
+        { "argb", FFV2AMD_PIX_ARGB, FFV2AMD_PIX_GBRP, 1, 4 },       { "rgba", FFV2AMD_PIX_RGBA, FFV2AMD_PIX_GBRP, 1, 4 },
+        { "abgr", FFV2AMD_PIX_ABGR, FFV2AMD_PIX_GBRP, 1, 4 },       { "bgra", FFV2AMD_PIX_BGRA, FFV2AMD_PIX_GBRP, 1, 4 },
+        { "0rgb", FFV2AMD_PIX_0RGB, FFV2AMD_PIX_GBRP, 1, 4 },       { "rgb0", FFV2AMD_PIX_RGB0, FFV2AMD_PIX_GBRP, 1, 4 },
+        { "0bgr", FFV2AMD_PIX_0BGR, FFV2AMD_PIX_GBRP, 1, 4 },       { "bgr0", FFV2AMD_PIX_BGR0, FFV2AMD_PIX_GBRP, 1, 4 },
+        { "rgb48be", FFV2AMD_PIX_RGB48BE, FFV2AMD_PIX_GBRP12LE, 2, 3 }, { "rgb48le", FFV2AMD_PIX_RGB48LE, FFV2AMD_PIX_GBRP12LE, 2, 3 },
+        { "bgr48be", FFV2AMD_PIX_BGR48BE, FFV2AMD_PIX_GBRP12LE, 2, 3 }, { "bgr48le", FFV2AMD_PIX_BGR48LE, FFV2AMD_PIX_GBRP12LE, 2, 3 },
+        { "rgba64be", FFV2AMD_PIX_RGBA64BE, FFV2AMD_PIX_GBRP12LE, 2, 4 }, { "rgba64le", FFV2AMD_PIX_RGBA64LE, FFV2AMD_PIX_GBRP12LE, 2, 4 },
+        { "bgra64be", FFV2AMD_PIX_BGRA64BE, FFV2AMD_PIX_GBRP12LE, 2, 4 }, { "bgra64le", FFV2AMD_PIX_BGRA64LE, FFV2AMD_PIX_GBRP12LE, 2, 4 },
+    };
+    *pk = 0;
+    for (size_t i = 0; i < sizeof(packed) / sizeof(packed[0]); i++)
+        if (!strcmp(s, packed[i].n)) { *planes = packed[i].nc; *bps = packed[i].bps; *sub = 0; *nv = 0; *pk = packed[i].src; return packed[i].id; }
     static const struct { const char *n; int id, bps, sub; unsigned flags; } semi[] = {
         { "nv12", FFV2AMD_PIX_YUV444P, 1, 420, FFV2AMD_FRAME_NV | FFV2AMD_FRAME_YUV420 },
         { "nv21", FFV2AMD_PIX_YUV444P, 1, 420, FFV2AMD_FRAME_NV | FFV2AMD_FRAME_NV_VU | FFV2AMD_FRAME_YUV420 },
@@ -67,13 +86,13 @@ int main(int argc, char **argv)
         fprintf(stderr, "usage: %s WIDTH HEIGHT PIX_FMT IN.yuv OUT.ffv2 [QP] [HIP_DEVICE] [--async N]\n", argv[0]);
         return 2;
     }
-    int planes = 0, bps = 0, sub = 0;
+    int planes = 0, bps = 0, sub = 0, pk = 0;
     unsigned nv = 0;
     FFV2AMDCodecContext ctx = { 0 };
     ctx.width = atoi(argv[1]);
     ctx.height = atoi(argv[2]);
-    ctx.pix_fmt = parse_fmt(argv[3], &planes, &bps, &sub, &nv);
-    if (sub && !strcmp(argv[argc - 1], "--no-convert")) {
+    ctx.pix_fmt = parse_fmt(argv[3], &planes, &bps, &sub, &nv, &pk);
+    if ((sub || pk) && !strcmp(argv[argc - 1], "--no-convert")) {
         fprintf(stderr, "%s is not an encoder input (ffv2enc.c:596-601)\n", argv[3]);
         return 2;
     }
@@ -99,7 +118,8 @@ int main(int argc, char **argv)
     const size_t cplane_bytes = (size_t)cw * ch * bps;
     /* a semi-planar frame: Y, then ch rows of cw interleaved pairs (data[1], 2 * cw samples a row) */
     const size_t frame_bytes = sub ? plane_bytes + 2 * cplane_bytes : plane_bytes * planes;
-    const unsigned sub_flag = nv ? nv : sub == 420 ? FFV2AMD_FRAME_YUV420 : sub == 422 ? FFV2AMD_FRAME_YUV422 : 0;
+    /* a packed RGB frame: h rows of w pixels of `planes` components (data[0]) */
+    const unsigned sub_flag = pk ? FFV2AMD_FRAME_PACKED | FFV2AMD_FRAME_SRC_FMT(pk) : nv ? nv : sub == 420 ? FFV2AMD_FRAME_YUV420 : sub == 422 ? FFV2AMD_FRAME_YUV422 : 0;
     uint8_t *buf = malloc(frame_bytes);
     if (!buf) return 1;
     long nframes = 0;
@@ -116,9 +136,9 @@ int main(int argc, char **argv)
             int have = !eof && fread(buf, 1, frame_bytes, in) == frame_bytes;
             FFV2AMDFrame fr = { 0 };
             if (!have) eof = 1;
-            for (int p = 0; p < planes && have; p++) {
+            for (int p = 0; p < (pk ? 1 : planes) && have; p++) {
                 fr.data[p] = sub ? (p ? buf + plane_bytes + (p - 1) * cplane_bytes : buf) : buf + p * plane_bytes;
-                fr.linesize[p] = (ptrdiff_t)(sub && p ? (nv ? 2 * cw : cw) : ctx.width) * bps;
+                fr.linesize[p] = (ptrdiff_t)(sub && p ? (nv ? 2 * cw : cw) : pk ? ctx.width * planes : ctx.width) * bps;
             }
             fr.pts = sent;
             for (;;) {
@@ -150,12 +170,13 @@ int main(int argc, char **argv)
         FFV2AMDFrame fr = { 0 };
         FFV2AMDPacket pkt = { 0 };
         int got = 0;
-        for (int p = 0; p < planes; p++) {
+        for (int p = 0; p < (pk ? 1 : planes); p++) {
             fr.data[p] = sub ? (p ? buf + plane_bytes + (p - 1) * cplane_bytes : buf) : buf + p * plane_bytes;
-            fr.linesize[p] = (ptrdiff_t)(sub && p ? (nv ? 2 * cw : cw) : ctx.width) * bps;
+            fr.linesize[p] = (ptrdiff_t)(sub && p ? (nv ? 2 * cw : cw) : pk ? ctx.width * planes : ctx.width) * bps;
         }
         fr.pts = nframes;
-        ret = nv ? ffv2amd_codec_encode_nv(&ctx, &pkt, &fr, nv, &got)
+        ret = pk ? ffv2amd_codec_encode_packed(&ctx, &pkt, &fr, pk, &got)
+            : nv ? ffv2amd_codec_encode_nv(&ctx, &pkt, &fr, nv, &got)
             : sub == 420 ? ffv2amd_codec_encode_yuv420(&ctx, &pkt, &fr, &got)
             : sub == 422 ? ffv2amd_codec_encode_yuv422(&ctx, &pkt, &fr, &got)
             : ffv2amd_codec_encode2(&ctx, &pkt, &fr, &got);

@@ -26,6 +26,8 @@ EXPORTS = [
     "ffv2amd_ring_send_422", "ffv2amd_qp_send_frame_422", "ffv2amd_debug_upconv422_time",
     "ffv2amd_frame_bytes_nv", "ffv2amd_convert_nv_device", "ffv2amd_encode_frame_nv", "ffv2amd_qp_send_frame_nv",
     "ffv2amd_debug_nv_time",
+    "ffv2amd_frame_bytes_packed", "ffv2amd_convert_packed_device", "ffv2amd_encode_frame_packed",
+    "ffv2amd_qp_send_frame_packed", "ffv2amd_debug_packed_time",
     "ffv2amd_lanecoder_open", "ffv2amd_lanecoder_open_ex", "ffv2amd_lanecoder_close", "ffv2amd_lanecoder_bytes_per_frame",
     "ffv2amd_lanecoder_bytes_per_frame_ex", "ffv2amd_lanecoder_encode",
     "ffv2amd_lanecoder_submit", "ffv2amd_lanecoder_finish", "ffv2amd_lanecoder_finish_packed", "ffv2amd_lanecoder_stats", "ffv2amd_debug_lanecoder_window", "ffv2amd_debug_pvq_time",
@@ -33,6 +35,7 @@ EXPORTS = [
     "ffv2amd_codec_init", "ffv2amd_codec_encode2", "ffv2amd_codec_close", "ffv2amd_codec_descriptor",
     "ffv2amd_codec_send_frame", "ffv2amd_codec_receive_packet", "ffv2amd_packet_unref", "ffv2amd_codec_encode_yuv420",
     "ffv2amd_codec_encode_yuv422", "ffv2amd_codec_encode_nv",
+    "ffv2amd_codec_encode_packed",
     # Matroska wire step (ffv2mkv.c)
     "ffv2amd_mkv_open", "ffv2amd_mkv_write_packet", "ffv2amd_mkv_close",
 ]
@@ -173,6 +176,15 @@ def load():
                                             C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.ffv2amd_qp_send_frame_nv.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_ssize_t), C.c_uint, C.c_int,
                                              C.c_int64]
+    lib.ffv2amd_frame_bytes_packed.argtypes = [C.c_void_p, C.c_int]
+    lib.ffv2amd_frame_bytes_packed.restype = C.c_size_t
+    lib.ffv2amd_convert_packed_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
+                                                  C.c_void_p, C.c_void_p]
+    lib.ffv2amd_debug_packed_time.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
+                                              C.c_void_p, C.c_int, C.POINTER(C.c_float)]
+    lib.ffv2amd_encode_frame_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_ssize_t, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.ffv2amd_qp_send_frame_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_ssize_t, C.c_int, C.c_int, C.c_int64]
     lib.ffv2amd_coded_gain.argtypes = [C.c_int64]
     lib.ffv2amd_coded_gain.restype = C.c_uint32
     lib.ffv2amd_range_prefix.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -389,7 +390,8 @@ void run_parallel(int n, int want, Fn fn)
 // What a frame's chroma is when it reaches the device: ready (4:4:4), or waiting for the up-conversion
 // (semi-planar sources: which one, see nv_kind)
 enum ChromaKind : uint8_t { CHROMA_444 = 0, CHROMA_420 = 1, CHROMA_422 = 2,
-                            CHROMA_NV12 = 3, CHROMA_NV21 = 4, CHROMA_P010 = 5, CHROMA_NV16 = 6, CHROMA_NV24 = 7, CHROMA_NV42 = 8 };
+                            CHROMA_NV12 = 3, CHROMA_NV21 = 4, CHROMA_P010 = 5, CHROMA_NV16 = 6, CHROMA_NV24 = 7, CHROMA_NV42 = 8,
+                            CHROMA_PACKED = 16 };   // packed RGB: CHROMA_PACKED + the source's index in PACKED_FMTS
 
 // A few persistent host threads that gather the rows of a caller's (pageable) frame into pinned
 // memory, slice by slice, each slice's DMA issued by the thread that gathered it.  The calling
@@ -665,6 +667,7 @@ struct ffv2amd_encoder {
     uint8_t *qd_c420[2] = { nullptr, nullptr };          // U, V of a 4:2:0 frame (ffv2amd_qp_send_frame_420)
     uint8_t *qd_c422[2] = { nullptr, nullptr };          // U, V of a 4:2:2 frame (ffv2amd_qp_send_frame_422)
     uint8_t *qd_cnv[2] = { nullptr, nullptr };           // interleaved chroma of a semi-planar frame (ffv2amd_qp_send_frame_nv)
+    uint8_t *qd_cpk[2] = { nullptr, nullptr }, *qh_cpk[2] = { nullptr, nullptr };   // a packed RGB frame (qp_send_frame_packed)
     int64_t q_tag[2] = { 0, 0 };
     // decoder-side check (ffv2amd_decode_frame)
     int16_t *d_dec_pulses = nullptr;
@@ -684,6 +687,8 @@ struct ffv2amd_encoder {
     uint8_t *d_422 = nullptr, *h_422 = nullptr;
     // semi-planar front end (ffv2amd_*_nv): a tight host frame on its way to the device (encode_frame_nv)
     uint8_t *d_nv = nullptr, *h_nv = nullptr;
+    // packed RGB front end (ffv2amd_*_packed): a host frame on its way to the device (encode_frame_packed)
+    uint8_t *d_pkf = nullptr, *h_pkf = nullptr;
     // asynchronous frame ring (ffv2amd_ring_*)
     struct RingSlot {
         uint8_t  *h_frame = nullptr, *d_frame = nullptr;    // pinned staging frame, device frame
@@ -695,6 +700,7 @@ struct ffv2amd_encoder {
         uint8_t  *d_c420 = nullptr;                         // U, V of a 4:2:0 frame, rows c_pitch apart (ring_send_420)
         uint8_t  *d_c422 = nullptr;                         // U, V of a 4:2:2 frame, h rows each (ring_send_422)
         uint8_t  *d_cnv = nullptr;                          // interleaved chroma of a semi-planar frame (ring_send + FRAME_NV)
+        uint8_t  *d_cpk = nullptr, *h_cpk = nullptr;        // a packed RGB frame and its pinned staging (ring_send + FRAME_PACKED)
         hipEvent_t ev_h2d = nullptr, ev_done = nullptr, ev_meta = nullptr;
         int64_t tag = 0;
     };
@@ -765,6 +771,7 @@ struct ffv2amd_encoder {
         uint8_t *d_c420[NBUF] = {};              // 4:2:0 chroma as it arrives: [cap][U plane, V plane]
         uint8_t *d_c422[NBUF] = {};              // 4:2:2 chroma as it arrives: [cap][U plane, V plane]
         uint8_t *d_cnv[NBUF] = {};               // semi-planar chroma as it arrives: [cap][nv_stage_bytes]
+        uint8_t *d_cpk[NBUF] = {};               // packed RGB frames as they arrive: [cap][packed_stage_bytes]
         int32_t *d_w[NBUF] = {};
         bool any_w[NBUF] = {};
         std::vector<int64_t> tags[NBUF];
@@ -780,6 +787,7 @@ struct ffv2amd_encoder {
         static constexpr int NBOUNCE = 64;       // at most; nbounce of them in use: about 256 MB (a copy queued behind the
         uint8_t *bounce[NBOUNCE] = {};           // coder's kernels takes a millisecond to start: with four frames of
         hipEvent_t ev_bounce[NBOUNCE] = {};      // bounce memory the sender waited for every one of them)
+        size_t bounce_cap[NBOUNCE] = {};         // bytes of each (a 4-component packed RGB frame needs more than frame_stride)
         int nbounce = 4;
         unsigned nb_seq = 0;
         GatherPool *pool = nullptr;              // helper threads for the row copies of pageable frames
@@ -889,6 +897,8 @@ void ffv2amd_encoder_destroy(ffv2amd_encoder *e)
     if (e->h_422) (void)hipHostFree(e->h_422);
     (void)hipFree(e->d_nv);
     if (e->h_nv) (void)hipHostFree(e->h_nv);
+    (void)hipFree(e->d_pkf);
+    if (e->h_pkf) (void)hipHostFree(e->h_pkf);
     lanecoder_free(e);
     for (auto &q : e->qset) {
         (void)hipFree(q.d_rec); (void)hipFree(q.d_stream); (void)hipFree(q.d_totals); (void)hipFree(q.d_codes); (void)hipFree(q.d_status);
@@ -906,6 +916,8 @@ void ffv2amd_encoder_destroy(ffv2amd_encoder *e)
     if (e->q_copy) { (void)hipStreamSynchronize(e->q_copy); (void)hipStreamDestroy(e->q_copy); }
     for (int k = 0; k < 2; k++) {
         (void)hipFree(e->qd_frame[k]); (void)hipFree(e->qd_w[k]); (void)hipFree(e->qd_c420[k]); (void)hipFree(e->qd_c422[k]); (void)hipFree(e->qd_cnv[k]);
+        (void)hipFree(e->qd_cpk[k]);
+        if (e->qh_cpk[k]) (void)hipHostFree(e->qh_cpk[k]);
         if (e->qh_frame[k]) (void)hipHostFree(e->qh_frame[k]);
     }
     (void)hipFree(e->d_thr); (void)hipFree(e->d_lds_scan); (void)hipFree(e->d_prefix);
@@ -1672,6 +1684,139 @@ int ffv2amd_encode_frame_nv(ffv2amd_encoder *e, const uint8_t *const data[2], co
     const size_t total = g.y_row * (size_t)in.height + g.uv_row * (size_t)g.ch;
     HIPCHK(hipMemcpyAsync(e->d_nv, e->h_nv, total, hipMemcpyHostToDevice, s));
     HIPCHK(nv_launch(e, k, 1, e->d_nv, g.y_row, 0, e->d_nv + g.y_row * (size_t)in.height, g.uv_row, 0, e->d_frame, s));
+    return encode_uploaded_frame(e, qp, nullptr, out, out_cap, out_size);
+}
+
+// ------------------------------------------------------------------
+// Packed RGB front end: rgb24 / bgra / rgb48le / ... sources (FFV2AMD_FRAME_PACKED) -- libswscale's unscaled
+// converters (swscale_unscaled.c:540-732, 1118-1190) are exact: a byte permutation, or a byte swap and a shift by
+// 16 - depth; rgb0 / bgr0 / 0rgb / 0bgr deliberately as their alpha forms -- see ffv2_packed.hip.
+// ------------------------------------------------------------------
+struct PackedFmt { int id, bps, nc; bool bgr, lead, swap; };
+static const PackedFmt PACKED_FMTS[] = {
+    { FFV2AMD_PIX_RGB24, 1, 3, false, false, false }, { FFV2AMD_PIX_BGR24, 1, 3, true, false, false },
+    { FFV2AMD_PIX_ARGB, 1, 4, false, true, false },   { FFV2AMD_PIX_RGBA, 1, 4, false, false, false },
+    { FFV2AMD_PIX_ABGR, 1, 4, true, true, false },    { FFV2AMD_PIX_BGRA, 1, 4, true, false, false },
+    { FFV2AMD_PIX_0RGB, 1, 4, false, true, false },   { FFV2AMD_PIX_RGB0, 1, 4, false, false, false },
+    { FFV2AMD_PIX_0BGR, 1, 4, true, true, false },    { FFV2AMD_PIX_BGR0, 1, 4, true, false, false },
+    { FFV2AMD_PIX_RGB48BE, 2, 3, false, false, true }, { FFV2AMD_PIX_RGB48LE, 2, 3, false, false, false },
+    { FFV2AMD_PIX_BGR48BE, 2, 3, true, false, true },  { FFV2AMD_PIX_BGR48LE, 2, 3, true, false, false },
+    { FFV2AMD_PIX_RGBA64BE, 2, 4, false, false, true }, { FFV2AMD_PIX_RGBA64LE, 2, 4, false, false, false },
+    { FFV2AMD_PIX_BGRA64BE, 2, 4, true, false, true },  { FFV2AMD_PIX_BGRA64LE, 2, 4, true, false, false },
+};
+static constexpr int N_PACKED_FMTS = (int)(sizeof(PACKED_FMTS) / sizeof(PACKED_FMTS[0]));
+static_assert(CHROMA_PACKED + N_PACKED_FMTS <= 256, "ChromaKind is a byte");
+
+// the source format and the encoder's -> the index into PACKED_FMTS; FFV2AMD_ERR_INVAL for every combination but
+// 8-bit sources into gbrp and 16-bit sources into gbrp10le / gbrp12le
+static int packed_kind(const ffv2amd_info &in, int src_fmt, int *idx)
+{
+    for (int i = 0; i < N_PACKED_FMTS; i++) {
+        if (PACKED_FMTS[i].id != src_fmt) continue;
+        if (in.planes != 3) return FFV2AMD_ERR_INVAL;
+        const bool ok = PACKED_FMTS[i].bps == 1 ? in.pix_fmt == FFV2AMD_PIX_GBRP
+                                                : in.pix_fmt == FFV2AMD_PIX_GBRP10LE || in.pix_fmt == FFV2AMD_PIX_GBRP12LE;
+        if (!ok) return FFV2AMD_ERR_INVAL;
+        *idx = i;
+        return FFV2AMD_OK;
+    }
+    return FFV2AMD_ERR_INVAL;
+}
+
+// flags with FFV2AMD_FRAME_PACKED: no other source-layout bit, and a source format the encoder takes
+static int packed_flags_kind(const ffv2amd_info &in, unsigned flags, int *idx)
+{
+    if (!(flags & FFV2AMD_FRAME_PACKED) ||
+        (flags & (FFV2AMD_FRAME_NV | FFV2AMD_FRAME_NV_VU | FFV2AMD_FRAME_YUV420 | FFV2AMD_FRAME_YUV422)))
+        return FFV2AMD_ERR_INVAL;
+    return packed_kind(in, (int)((flags >> 16) & 0xffu), idx);
+}
+
+static size_t packed_row(const ffv2amd_info &in, int idx) { return (size_t)in.width * PACKED_FMTS[idx].nc * PACKED_FMTS[idx].bps; }
+// staging rows are 128-byte aligned (the kernel's 16-byte loads need 16); enough for every format of the encoder's depth
+static size_t packed_pitch(const ffv2amd_info &in, int idx) { return align_up(packed_row(in, idx), 128); }
+static size_t packed_stage_bytes(const ffv2amd_info &in)
+{
+    return align_up((size_t)in.width * 4 * (in.depth > 8 ? 2 : 1), 128) * (size_t)in.height;
+}
+
+static hipError_t packed_launch(ffv2amd_encoder *e, int idx, int nframes, const uint8_t *src, size_t pitch,
+                                size_t frame_stride, uint8_t *dst, hipStream_t s)
+{
+    const PackedFmt &f = PACKED_FMTS[idx];
+    const FFV2PackedSrc ps{ src, pitch, frame_stride, f.bps, f.nc, f.bgr, f.lead, f.swap };
+    return ffv2_launch_packed(e->geom, nframes, ps, dst, s);
+}
+
+size_t ffv2amd_frame_bytes_packed(const ffv2amd_encoder *e, int src_fmt)
+{
+    int idx;
+    if (!e || packed_kind(e->info, src_fmt, &idx) < 0) return 0;
+    return packed_row(e->info, idx) * (size_t)e->info.height;
+}
+
+int ffv2amd_convert_packed_device(ffv2amd_encoder *e, int nframes, const void *d_src, size_t src_pitch,
+                                  size_t frame_stride, int src_fmt, void *d_frames444, void *stream)
+{
+    if (!e || !d_src || !d_frames444 || nframes < 1) return FFV2AMD_ERR_INVAL;
+    int idx;
+    int r = packed_kind(e->info, src_fmt, &idx);
+    if (r < 0) return r;
+    if (src_pitch < packed_row(e->info, idx)) return FFV2AMD_ERR_INVAL;
+    if (PACKED_FMTS[idx].bps == 2 && ((uintptr_t)d_frames444 & 1)) return FFV2AMD_ERR_INVAL;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return FFV2AMD_ERR_DEVICE;
+    HIPCHK(packed_launch(e, idx, nframes, (const uint8_t *)d_src, src_pitch, frame_stride, (uint8_t *)d_frames444,
+                         (hipStream_t)stream));
+    return FFV2AMD_OK;
+}
+
+int ffv2amd_debug_packed_time(ffv2amd_encoder *e, int nframes, const void *d_src, size_t src_pitch, size_t frame_stride,
+                              int src_fmt, void *d_frames444, int reps, float *ms_per_launch)
+{
+    if (!ms_per_launch || reps < 1) return FFV2AMD_ERR_INVAL;
+    int r = ffv2amd_convert_packed_device(e, nframes, d_src, src_pitch, frame_stride, src_fmt, d_frames444, e ? e->stream : nullptr);
+    if (r < 0) return r;                                           // (the warm-up launch)
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return FFV2AMD_ERR_DEVICE;
+    hipStream_t s = e->stream;
+    hipEvent_t a, b;
+    HIPCHK(hipEventCreate(&a));
+    HIPCHK(hipEventCreate(&b));
+    HIPCHK(hipEventRecord(a, s));
+    for (int i = 0; i < reps; i++) {
+        r = ffv2amd_convert_packed_device(e, nframes, d_src, src_pitch, frame_stride, src_fmt, d_frames444, s);
+        if (r < 0) break;
+    }
+    HIPCHK(hipEventRecord(b, s));
+    HIPCHK(hipEventSynchronize(b));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, a, b));
+    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+    if (r < 0) return r;
+    *ms_per_launch = ms / reps;
+    return FFV2AMD_OK;
+}
+
+int ffv2amd_encode_frame_packed(ffv2amd_encoder *e, const uint8_t *data, ptrdiff_t linesize, int src_fmt,
+                                int qp, uint8_t *out, size_t out_cap, size_t *out_size)
+{
+    if (!e || !data || !out || !out_size) return FFV2AMD_ERR_INVAL;
+    int idx;
+    int r = packed_kind(e->info, src_fmt, &idx);
+    if (r < 0) return r;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return FFV2AMD_ERR_DEVICE;
+    const ffv2amd_info &in = e->info;
+    if (!e->d_pkf) {
+        HIPCHK(hipMalloc(&e->d_pkf, packed_stage_bytes(in)));
+        HIPCHK(hipHostMalloc(&e->h_pkf, packed_stage_bytes(in), hipHostMallocDefault));
+    }
+    const size_t row = packed_row(in, idx), pitch = packed_pitch(in, idx);
+    for (int y = 0; y < in.height; y++) memcpy(e->h_pkf + (size_t)y * pitch, data + (ptrdiff_t)y * linesize, row);
+    hipStream_t s = e->stream;
+    HIPCHK(hipMemcpyAsync(e->d_pkf, e->h_pkf, pitch * (size_t)(in.height - 1) + row, hipMemcpyHostToDevice, s));
+    HIPCHK(packed_launch(e, idx, 1, e->d_pkf, pitch, 0, e->d_frame, s));
     return encode_uploaded_frame(e, qp, nullptr, out, out_cap, out_size);
 }
 
@@ -2660,6 +2805,40 @@ int ffv2amd_qp_send_frame_nv(ffv2amd_encoder *e, const uint8_t *const data[2], c
     return FFV2AMD_OK;
 }
 
+// ... and for a packed RGB frame (data rows `linesize` bytes apart; src_fmt as for ffv2amd_encode_frame_packed)
+int ffv2amd_qp_send_frame_packed(ffv2amd_encoder *e, const uint8_t *data, ptrdiff_t linesize, int src_fmt, int qp, int64_t tag)
+{
+    if (!e || !data) return FFV2AMD_ERR_INVAL;
+    int idx;
+    int r = packed_kind(e->info, src_fmt, &idx);
+    if (r < 0) return r;
+    if (qp < 1 || qp > 64) return FFV2AMD_ERR_UNSUPPORTED;
+    if (e->q_sub - e->q_fin >= 2) return FFV2AMD_ERR_AGAIN;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return FFV2AMD_ERR_DEVICE;
+    const ffv2amd_info &in = e->info;
+    const int q = (int)(e->q_sub & 1u);
+    if (!e->qd_frame[q]) {
+        HIPCHK(hipMalloc(&e->qd_frame[q], in.frame_stride));
+        HIPCHK(hipMalloc(&e->qd_w[q], sizeof(int32_t) * in.block_planes));
+        HIPCHK(hipHostMalloc(&e->qh_frame[q], in.frame_stride, hipHostMallocDefault));
+        memset(e->qh_frame[q], 0, in.frame_stride);
+    }
+    if (!e->qd_cpk[q]) {
+        HIPCHK(hipMalloc(&e->qd_cpk[q], packed_stage_bytes(in)));
+        HIPCHK(hipHostMalloc(&e->qh_cpk[q], packed_stage_bytes(in), hipHostMallocDefault));
+    }
+    const size_t row = packed_row(in, idx), pitch = packed_pitch(in, idx);
+    for (int y = 0; y < in.height; y++) memcpy(e->qh_cpk[q] + (size_t)y * pitch, data + (ptrdiff_t)y * linesize, row);
+    hipStream_t s = e->stream;
+    HIPCHK(hipMemcpyAsync(e->qd_cpk[q], e->qh_cpk[q], pitch * (size_t)(in.height - 1) + row, hipMemcpyHostToDevice, s));
+    HIPCHK(packed_launch(e, idx, 1, e->qd_cpk[q], pitch, 0, e->qd_frame[q], s));
+    r = ffv2amd_qp_submit(e, 1, e->qd_frame[q], qp, nullptr);
+    if (r < 0) return r;
+    e->q_tag[q] = tag;
+    return FFV2AMD_OK;
+}
+
 int ffv2amd_qp_receive_packet(ffv2amd_encoder *e, uint8_t *out, size_t out_cap, size_t *out_size, int64_t *tag)
 {
     if (!e || !out || !out_size) return FFV2AMD_ERR_INVAL;
@@ -2697,13 +2876,15 @@ int ffv2amd_qpring_close(ffv2amd_encoder *e)
     (void)ffv2amd_lanecoder_close(e);
     for (int i = 0; i < ffv2amd_encoder::QpRing::NBUF; i++) {
         (void)hipFree(r.d_frames[i]); (void)hipFree(r.d_c420[i]); (void)hipFree(r.d_c422[i]); (void)hipFree(r.d_cnv[i]); (void)hipFree(r.d_w[i]);
+        (void)hipFree(r.d_cpk[i]);
         r.d_frames[i] = nullptr; r.d_c420[i] = nullptr; r.d_c422[i] = nullptr; r.d_cnv[i] = nullptr; r.d_w[i] = nullptr;
+        r.d_cpk[i] = nullptr;
         r.any_w[i] = false; r.tags[i].clear();
     }
     for (int i = 0; i < ffv2amd_encoder::QpRing::NBOUNCE; i++) {
         if (r.bounce[i]) (void)hipHostFree(r.bounce[i]);
         if (r.ev_bounce[i]) (void)hipEventDestroy(r.ev_bounce[i]);
-        r.bounce[i] = nullptr; r.ev_bounce[i] = nullptr;
+        r.bounce[i] = nullptr; r.ev_bounce[i] = nullptr; r.bounce_cap[i] = 0;
     }
     if (r.h_buf) (void)hipHostFree(r.h_buf);
     r.h_buf = nullptr; r.h_cap = 0;
@@ -2851,7 +3032,12 @@ static int qpring_submit(ffv2amd_encoder *e)
             if (kind == CHROMA_420)
                 HIPCHK(ffv2_launch_upconv_chroma(e->upconv, e->geom, i1 - i0, r.d_c420[b] + (size_t)i0 * c_frame, c_pitch,
                                                  c_pitch * (size_t)ch, c_frame, r.d_frames[b] + (size_t)i0 * in.frame_stride, e->stream));
-            else if (kind != CHROMA_422) {     // semi-planar: luma in plane 0 already (P010: shifted there in place)
+            else if (kind >= CHROMA_PACKED) {  // packed RGB: the whole frame waits in staging
+                const int idx = kind - CHROMA_PACKED;
+                const size_t st = packed_stage_bytes(in);
+                HIPCHK(packed_launch(e, idx, i1 - i0, r.d_cpk[b] + (size_t)i0 * st, packed_pitch(in, idx), st,
+                                     r.d_frames[b] + (size_t)i0 * in.frame_stride, e->stream));
+            } else if (kind != CHROMA_422) {     // semi-planar: luma in plane 0 already (P010: shifted there in place)
                 uint8_t *d0 = r.d_frames[b] + (size_t)i0 * in.frame_stride;
                 const size_t st = nv_stage_bytes(in);
                 HIPCHK(nv_launch(e, (ChromaKind)kind, i1 - i0, d0, in.row_pitch, in.frame_stride, r.d_cnv[b] + (size_t)i0 * st,
@@ -2892,8 +3078,14 @@ int ffv2amd_qpring_send(ffv2amd_encoder *e, const uint8_t *const data[4], const 
         const int rc = nv_kind(in, flags, &nvk);
         if (rc < 0) return rc;
     }
+    const bool pk = (flags & FFV2AMD_FRAME_PACKED) != 0;           // data = the packed RGB plane
+    int pki = 0;
+    if (pk) {
+        const int rc = packed_flags_kind(in, flags, &pki);
+        if (rc < 0) return rc;
+    }
     const bool sub = (is420 || is422) && !nv;                    // chroma goes to staging, luma into plane 0
-    const int npl = nv ? 2 : sub ? 3 : in.planes;
+    const int npl = pk ? 1 : nv ? 2 : sub ? 3 : in.planes;
     if (sub && in.planes != 3) return FFV2AMD_ERR_INVAL;
     for (int p = 0; p < npl; p++)
         if (!data[p]) return FFV2AMD_ERR_INVAL;
@@ -2922,6 +3114,7 @@ int ffv2amd_qpring_send(ffv2amd_encoder *e, const uint8_t *const data[4], const 
         if (rc < 0) return rc;
         if (!r.d_cnv[b]) HIPCHK(hipMalloc(&r.d_cnv[b], nv_stage_bytes(in) * (size_t)r.cap));
     }
+    if (pk && !r.d_cpk[b]) HIPCHK(hipMalloc(&r.d_cpk[b], packed_stage_bytes(in) * (size_t)r.cap));
     uint8_t *d_frame = r.d_frames[b] + (size_t)r.count * in.frame_stride;
     uint8_t *d_c = sub ? (is422 ? r.d_c422[b] : r.d_c420[b]) + (size_t)r.count * 2 * c_pitch * (size_t)ch : nullptr;
     // where each plane goes: rows `pitch` apart on the device
@@ -2939,6 +3132,9 @@ int ffv2amd_qpring_send(ffv2amd_encoder *e, const uint8_t *const data[4], const 
         pl[0] = Pl{ data[0], linesize[0], g.y_row, in.row_pitch, in.height, d_frame };
         pl[1] = Pl{ data[1], linesize[1], g.uv_row, nv_uv_pitch(g), g.ch, r.d_cnv[b] + (size_t)r.count * nv_stage_bytes(in) };
     }
+    if (pk)
+        pl[0] = Pl{ data[0], linesize[0], packed_row(in, pki), packed_pitch(in, pki), in.height,
+                    r.d_cpk[b] + (size_t)r.count * packed_stage_bytes(in) };
     hipStream_t sh = r.h2d;
     bool in_place = (flags & FFV2AMD_FRAME_PINNED) != 0;
     if (!in_place && (flags & FFV2AMD_FRAME_REGISTER)) {         // pageable memory from a pool: page-locked on first sight
@@ -2958,11 +3154,19 @@ int ffv2amd_qpring_send(ffv2amd_encoder *e, const uint8_t *const data[4], const 
         // pageable memory: through one of a few page-locked frames (complete when the call returns as far as the caller
         // is concerned: its rows are copied here)
         const int k = (int)(r.nb_seq++ % (unsigned)r.nbounce);
+        const size_t need = pk ? std::max(in.frame_stride, packed_stage_bytes(in)) : in.frame_stride;
         if (!r.bounce[k]) {
-            HIPCHK(hipHostMalloc(&r.bounce[k], in.frame_stride, hipHostMallocDefault));
+            HIPCHK(hipHostMalloc(&r.bounce[k], need, hipHostMallocDefault));
             HIPCHK(hipEventCreateWithFlags(&r.ev_bounce[k], hipEventDisableTiming));
+            r.bounce_cap[k] = need;
         } else {
             HIPCHK(hipEventSynchronize(r.ev_bounce[k]));
+            if (r.bounce_cap[k] < need) {                        // a packed RGB frame larger than the planar ones
+                (void)hipHostFree(r.bounce[k]);
+                r.bounce[k] = nullptr; r.bounce_cap[k] = 0;
+                HIPCHK(hipHostMalloc(&r.bounce[k], need, hipHostMallocDefault));
+                r.bounce_cap[k] = need;
+            }
         }
         // rows are copied in slices, by the ring's helper threads where the picture is large enough to pay for the
         // hand-over (FFV2AMD_GATHER_THREADS, caller included); then one DMA per run of planes that lie back to back on
@@ -2998,7 +3202,7 @@ int ffv2amd_qpring_send(ffv2amd_encoder *e, const uint8_t *const data[4], const 
         }
         HIPCHK(hipEventRecord(r.ev_bounce[k], sh));
     }
-    r.chroma[b][(size_t)r.count] = nv ? nvk : is420 ? CHROMA_420 : is422 ? CHROMA_422 : CHROMA_444;   // converted when the batch leaves (qpring_submit)
+    r.chroma[b][(size_t)r.count] = pk ? (uint8_t)(CHROMA_PACKED + pki) : nv ? nvk : is420 ? CHROMA_420 : is422 ? CHROMA_422 : CHROMA_444;   // converted when the batch leaves (qpring_submit)
     if (W) {
         if (!r.d_w[b]) HIPCHK(hipMalloc(&r.d_w[b], sizeof(int32_t) * nb * (size_t)r.cap));
         if (!r.any_w[b]) {
@@ -3184,6 +3388,8 @@ void ffv2amd_ring_close(ffv2amd_encoder *e)
     for (auto &r : e->ring) {
         (void)hipFree(r.d_frame); (void)hipFree(r.d_pkt); (void)hipFree(r.d_meta);
         (void)hipFree(r.d_codes); (void)hipFree(r.d_bitcnt); (void)hipFree(r.d_w); (void)hipFree(r.d_c420); (void)hipFree(r.d_c422); (void)hipFree(r.d_cnv);
+        (void)hipFree(r.d_cpk);
+        if (r.h_cpk) (void)hipHostFree(r.h_cpk);
         if (r.h_frame) (void)hipHostFree(r.h_frame);
         if (r.h_pkt) (void)hipHostFree(r.h_pkt);
         if (r.h_meta) (void)hipHostFree(r.h_meta);
@@ -3364,6 +3570,8 @@ static int ring_submit(ffv2amd_encoder *e, ffv2amd_encoder::RingSlot &r, const R
     else if (chroma == CHROMA_422)
         HIPCHK(ffv2_launch_upconv422_chroma(e->upconv422, e->geom, 1, r.d_c422, pl[1].pitch, pl[1].pitch * (size_t)pl[1].rows, 0,
                                             r.d_frame, sc));
+    else if (chroma >= CHROMA_PACKED)          // packed RGB: the whole frame is in staging
+        HIPCHK(packed_launch(e, chroma - CHROMA_PACKED, 1, r.d_cpk, pl[0].pitch, 0, r.d_frame, sc));
     else if (chroma != CHROMA_444)             // semi-planar: luma is in plane 0 already (P010: shifted there in place)
         HIPCHK(nv_launch(e, chroma, 1, r.d_frame, in.row_pitch, 0, r.d_cnv, pl[1].pitch, 0, r.d_frame, sc));
     int rc = launch_encode_qp0(e, 1, r.d_frame, dW, r.d_pkt, in.packet_cap, r.d_meta, (int32_t *)(r.d_meta + 1),
@@ -3406,10 +3614,34 @@ static int ring_send_nv(ffv2amd_encoder *e, const uint8_t *const data[4], const 
     return ring_submit(e, r, pl, 2, k, W, tag, flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_REGISTER));
 }
 
+// a packed RGB frame through the ring: data[0] crosses PCIe as it is, into a staging area of the slot, and is
+// converted on the frame's compute stream (ffv2_packed.hip)
+static int ring_send_packed(ffv2amd_encoder *e, const uint8_t *const data[4], const ptrdiff_t linesize[4],
+                            const int32_t *W, int64_t tag, unsigned flags)
+{
+    const ffv2amd_info &in = e->info;
+    int idx;
+    int rc = packed_flags_kind(in, flags, &idx);
+    if (rc < 0) return rc;
+    if (!data[0]) return FFV2AMD_ERR_INVAL;
+    if (e->ring_count == (int)e->ring.size()) return FFV2AMD_ERR_AGAIN;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return FFV2AMD_ERR_DEVICE;
+    auto &r = e->ring[(size_t)((e->ring_head + e->ring_count) % (int)e->ring.size())];
+    if (!r.d_cpk) HIPCHK(hipMalloc(&r.d_cpk, packed_stage_bytes(in)));
+    // pinned staging of a pageable frame (or one of a FFV2AMD_FRAME_REGISTER pool seen for the first time)
+    if (!(flags & FFV2AMD_FRAME_PINNED) && !r.h_cpk) HIPCHK(hipHostMalloc(&r.h_cpk, packed_stage_bytes(in), hipHostMallocDefault));
+    RingPlane pl[1] = {
+        RingPlane{ data[0], linesize[0], packed_row(in, idx), packed_pitch(in, idx), in.height, 4, r.d_cpk, r.h_cpk },
+    };
+    return ring_submit(e, r, pl, 1, (ChromaKind)(CHROMA_PACKED + idx), W, tag, flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_REGISTER));
+}
+
 int ffv2amd_ring_send(ffv2amd_encoder *e, const uint8_t *const data[4], const ptrdiff_t linesize[4],
                       const int32_t *W, int64_t tag, unsigned flags)
 {
     if (!e || !data || !linesize || e->ring.empty()) return FFV2AMD_ERR_INVAL;
+    if (flags & FFV2AMD_FRAME_PACKED) return ring_send_packed(e, data, linesize, W, tag, flags);
     if (flags & (FFV2AMD_FRAME_NV | FFV2AMD_FRAME_NV_VU)) return ring_send_nv(e, data, linesize, W, tag, flags);
     const ffv2amd_info &in = e->info;
     for (int p = 0; p < in.planes; p++)

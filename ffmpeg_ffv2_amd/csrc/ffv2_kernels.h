@@ -114,6 +114,18 @@ hipError_t ffv2_launch_nv420(const FFV2Upconv *u, const FFV2Geom &g, int nframes
 hipError_t ffv2_launch_nv422(const FFV2Upconv422 *u, const FFV2Geom &g, int nframes, const FFV2NvSrc &src, uint8_t *dst,
                              hipStream_t s);
 hipError_t ffv2_launch_nv444(const FFV2Geom &g, int nframes, const FFV2NvSrc &src, uint8_t *dst, hipStream_t s);
+// packed RGB sources -> gbrp* (ffv2_packed.hip): libswscale's unscaled byte permutation (8 bit) or byte swap + shift
+// by 16 - depth (16 bit).  Only the picture's samples of planes 0..2 are written, never a row's padding.
+struct FFV2PackedSrc {
+    const uint8_t *src;        // frame 0's packed rows, pitch bytes apart (any alignment)
+    size_t pitch;
+    size_t frame_stride;       // frame f at src + f * frame_stride
+    int bps, nc;               // bytes per sample (the encoder's), components per pixel (3, 4)
+    bool bgr;                  // B first (bgr24, bgra, abgr, bgr48, bgra64, bgr0, 0bgr)
+    bool lead;                 // a byte before the components (argb, abgr, 0rgb, 0bgr)
+    bool swap;                 // big-endian 16-bit samples
+};
+hipError_t ffv2_launch_packed(const FFV2Geom &g, int nframes, const FFV2PackedSrc &src, uint8_t *dst, hipStream_t s);
 
 // qp > 0 entropy coder on the device (ffv2_rangecoder.hip): one wavefront per frame
 struct FFV2RangeCoderArgs {

@@ -237,6 +237,34 @@ int ffv2amd_codec_encode_nv(FFV2AMDCodecContext *avctx, FFV2AMDPacket *avpkt,
     return 0;
 }
 
+/* The same for a packed RGB source (rgb24, bgra, rgb48le, ...: frame->data[0] = the packed plane; src_fmt one of
+ * the FFV2AMD_PIX_* source formats of ffv2_amd.h): av_find_best_pix_fmt_of_2 (libavutil/pixdesc.c:2714-2873)
+ * selects gbrp (8 bit) or gbrp12le (16 bit), libswscale's unscaled converters permute the bytes or byte-swap and
+ * shift (swscale_unscaled.c:540-732, 1118-1190, exact), then encode2() runs.  rgb0 / bgr0 / 0rgb / 0bgr have no
+ * reference output and are converted as their alpha forms. */
+int ffv2amd_codec_encode_packed(FFV2AMDCodecContext *avctx, FFV2AMDPacket *avpkt,
+                                const FFV2AMDFrame *frame, int src_fmt, int *got_packet_ptr)
+{
+    FFV2AMDEncCtx *s;
+    size_t n = 0;
+    int ret;
+    if (!avctx || !avctx->priv_data || !avpkt || !frame || !got_packet_ptr)
+        return FFV2AMD_ERR_INVAL;
+    s = avctx->priv_data;
+    *got_packet_ptr = 0;
+    if (avctx->global_quality > 0 && s->scratch_cap < s->info.packet_cap_qp)
+        return FFV2AMD_ERR_NOSPACE;
+    ret = ffv2amd_encode_frame_packed(s->enc, frame->data[0], frame->linesize[0], src_fmt,
+                                      avctx->global_quality, s->scratch, s->scratch_cap, &n);
+    if (ret < 0)
+        return ret;
+    ret = hand_over(s, avpkt, n, frame->pts);
+    if (ret < 0)
+        return ret;
+    *got_packet_ptr = 1;
+    return 0;
+}
+
 /* avcodec_send_frame / avcodec_receive_packet (encode.c:420,449): the caller is ONE thread feeding
  * frames and collecting packets; frames are independent (ffv2enc.c:461-469), so frame n goes to
  * device n % ndev -- each device has its own encoder and asynchronous ring (global_quality 0) or
@@ -247,6 +275,7 @@ int ffv2amd_codec_send_frame(FFV2AMDCodecContext *avctx, const FFV2AMDFrame *fra
     ffv2amd_encoder *enc;
     const int qp = avctx ? avctx->global_quality : 0;
     unsigned nv;                                /* a semi-planar frame: its FFV2AMD_FRAME_NV* and subsampling flags */
+    unsigned packed;                            /* a packed RGB frame: FFV2AMD_FRAME_PACKED and its source format field */
     int ret, mode;
     if (!avctx || !avctx->priv_data || qp < 0)
         return FFV2AMD_ERR_INVAL;
@@ -257,6 +286,9 @@ int ffv2amd_codec_send_frame(FFV2AMDCodecContext *avctx, const FFV2AMDFrame *fra
     nv = flags & (FFV2AMD_FRAME_NV | FFV2AMD_FRAME_NV_VU | FFV2AMD_FRAME_YUV420 | FFV2AMD_FRAME_YUV422);
     if (!(flags & FFV2AMD_FRAME_NV))
         nv = 0;
+    packed = flags & FFV2AMD_FRAME_PACKED ? flags & (FFV2AMD_FRAME_PACKED | FFV2AMD_FRAME_SRC_FMT(0xff)) : 0;
+    if (packed && (flags & (FFV2AMD_FRAME_NV | FFV2AMD_FRAME_NV_VU | FFV2AMD_FRAME_YUV420 | FFV2AMD_FRAME_YUV422)))
+        return FFV2AMD_ERR_INVAL;
     s = avctx->priv_data;
     if (!frame) {                               /* end of stream: batches that are not full yet go out */
         if (s->mode == 3)
@@ -285,10 +317,12 @@ int ffv2amd_codec_send_frame(FFV2AMDCodecContext *avctx, const FFV2AMDFrame *fra
             s->qpring_qp = qp;
         }
         ret = ffv2amd_qpring_send(enc, frame->data, frame->linesize, NULL, frame->pts,
-                                  flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_YUV420 | FFV2AMD_FRAME_YUV422 | FFV2AMD_FRAME_REGISTER |
-                                           FFV2AMD_FRAME_NV | FFV2AMD_FRAME_NV_VU));
+                                  (flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_YUV420 | FFV2AMD_FRAME_YUV422 | FFV2AMD_FRAME_REGISTER |
+                                            FFV2AMD_FRAME_NV | FFV2AMD_FRAME_NV_VU)) | packed);
     } else if (mode == 2) {
-        ret = nv
+        ret = packed
+            ? ffv2amd_qp_send_frame_packed(enc, frame->data[0], frame->linesize[0], (int)(packed >> 16), qp, frame->pts)
+            : nv
             ? ffv2amd_qp_send_frame_nv(enc, (const uint8_t *const *)frame->data, frame->linesize, nv, qp, frame->pts)
             : flags & FFV2AMD_FRAME_YUV420
             ? ffv2amd_qp_send_frame_420(enc, frame->data, frame->linesize, qp, frame->pts)
@@ -305,7 +339,9 @@ int ffv2amd_codec_send_frame(FFV2AMDCodecContext *avctx, const FFV2AMDFrame *fra
                 }
             s->ring_open = 1;
         }
-        ret = nv
+        ret = packed
+            ? ffv2amd_ring_send(enc, frame->data, frame->linesize, NULL, frame->pts, packed | (flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_REGISTER)))
+            : nv
             ? ffv2amd_ring_send(enc, frame->data, frame->linesize, NULL, frame->pts, nv | (flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_REGISTER)))
             : flags & FFV2AMD_FRAME_YUV420
             ? ffv2amd_ring_send_420(enc, frame->data, frame->linesize, NULL, frame->pts, flags & (FFV2AMD_FRAME_PINNED | FFV2AMD_FRAME_REGISTER))

@@ -24,6 +24,22 @@ NV_FORMATS = {
     "nv24": (FRAME_NV, 8), "nv42": (FRAME_NV | FRAME_NV_VU, 8),
 }
 
+# packed RGB source formats -> (FFV2AMD_PIX_* / AVPixelFormat value, bytes per sample, components per pixel).  8-bit
+# ones go with a gbrp encoder, 16-bit ones with gbrp10le / gbrp12le.  Arrays hold the format's bytes as they lie in
+# memory: (H, W, C) uint8, or uint16 whose byte order is the format's (">u2" for the *be formats).
+FRAME_PACKED = 64
+PACKED_FORMATS = {
+    "rgb24": (2, 1, 3), "bgr24": (3, 1, 3), "argb": (25, 1, 4), "rgba": (26, 1, 4), "abgr": (27, 1, 4),
+    "bgra": (28, 1, 4), "0rgb": (120, 1, 4), "rgb0": (121, 1, 4), "0bgr": (122, 1, 4), "bgr0": (123, 1, 4),
+    "rgb48be": (34, 2, 3), "rgb48le": (35, 2, 3), "bgr48be": (59, 2, 3), "bgr48le": (60, 2, 3),
+    "rgba64be": (106, 2, 4), "rgba64le": (107, 2, 4), "bgra64be": (108, 2, 4), "bgra64le": (109, 2, 4),
+}
+
+
+def packed_frame_flags(fmt):
+    """FFV2AMD_FRAME_PACKED | FFV2AMD_FRAME_SRC_FMT(fmt) for ring_send / qpring_send / codec_send_frame."""
+    return FRAME_PACKED | PACKED_FORMATS[fmt][0] << 16
+
 
 class FFV2Encoder:
     def __init__(self, width, height, pix_fmt="yuv444p", device=0, max_batch=1):
@@ -320,6 +336,71 @@ class FFV2Encoder:
         _lib.check(self._lib.ffv2amd_convert_nv_device(
             self._h, F, y.data_ptr(), y.stride(1) * isz, uv.data_ptr(), uv.stride(1) * isz, y.stride(0) * isz if F > 1 else 0,
             flags, out.data_ptr(), C.c_void_p(stream)), "ffv2amd_convert_nv_device")
+        return out
+
+    # -- packed RGB front end (rgb24 bgr24 rgba bgra argb abgr rgb0 bgr0 0rgb 0bgr rgb48* bgr48* rgba64* bgra64*) --
+    def packed_fmt(self, fmt):
+        """The FFV2AMD_PIX_* value of a packed RGB format name; FFV2Error(-22) for a name this encoder does not take
+        (8-bit formats need a gbrp encoder, 16-bit ones gbrp10le / gbrp12le)."""
+        gbrp = {1: (73,), 2: (77, 137)}
+        if fmt not in PACKED_FORMATS or self.info.pix_fmt not in gbrp[PACKED_FORMATS[fmt][1]]:
+            raise _lib.FFV2Error(-22, "packed format %s for pix_fmt %d" % (fmt, self.info.pix_fmt))
+        return PACKED_FORMATS[fmt][0]
+
+    def packed_shape(self, fmt):
+        self.packed_fmt(fmt)
+        return self.info.height, self.info.width, PACKED_FORMATS[fmt][2]
+
+    def packed_dtype(self, fmt):
+        """uint8, or uint16 in the format's byte order."""
+        self.packed_fmt(fmt)
+        bps = PACKED_FORMATS[fmt][1]
+        return np.dtype(np.uint8) if bps == 1 else np.dtype(">u2" if fmt.endswith("be") else "<u2")
+
+    def _packed_host(self, src, fmt, copy=True):
+        shp, dt = self.packed_shape(fmt), self.packed_dtype(fmt)
+        if copy:
+            src = np.ascontiguousarray(src)
+        assert src.dtype.itemsize == dt.itemsize and src.shape == shp, (src.dtype, src.shape, shp)
+        assert src.strides[2] == dt.itemsize and src.strides[1] == shp[2] * dt.itemsize, src.strides
+        return src, src.ctypes.data, src.strides[0]
+
+    def frame_bytes_packed(self, fmt):
+        return self._lib.ffv2amd_frame_bytes_packed(self._h, self.packed_fmt(fmt))
+
+    def encode2_packed(self, src, fmt, qp=0):
+        """Packed RGB host frame (H, W, C) -> packet bytes."""
+        pf = self.packed_fmt(fmt)
+        keep, ptr, ls = self._packed_host(src, fmt)
+        out = np.empty(self.info.packet_cap if qp == 0 else self.info.packet_cap_qp, np.uint8)
+        n = C.c_size_t(0)
+        _lib.check(self._lib.ffv2amd_encode_frame_packed(self._h, ptr, ls, pf, qp, out.ctypes.data_as(C.c_void_p), out.size,
+                                                         C.byref(n)), "ffv2amd_encode_frame_packed")
+        del keep
+        return out[: n.value].tobytes()
+
+    def convert_packed(self, src, fmt, out=None, stream=None):
+        """Packed RGB frames resident on the device -> the (F, frame_stride) uint8 gbrp* batch for
+        encode_batch_device, asynchronously on `stream` (default: torch's current stream).  src: (H, W, C) or
+        (F, H, W, C) torch tensor of 8- or 16-bit samples (the format's bytes in memory), unit stride within a pixel;
+        rows and frames may be strided views into a larger allocation: the pitch and frame stride come from the
+        strides."""
+        import torch
+        pf = self.packed_fmt(fmt)
+        shp = self.packed_shape(fmt)
+        if src.dim() == 3:
+            src = src.unsqueeze(0)
+        F = src.shape[0]
+        isz = PACKED_FORMATS[fmt][1]
+        assert src.element_size() == isz, src.dtype
+        assert tuple(src.shape[1:]) == shp and src.stride(3) == 1 and src.stride(2) == shp[2], (tuple(src.shape), src.stride())
+        if out is None:
+            out = torch.empty((F, self.info.frame_stride), dtype=torch.uint8, device=src.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(src.device).cuda_stream
+        _lib.check(self._lib.ffv2amd_convert_packed_device(
+            self._h, F, src.data_ptr(), src.stride(1) * isz, src.stride(0) * isz if F > 1 else 0, pf, out.data_ptr(),
+            C.c_void_p(stream)), "ffv2amd_convert_packed_device")
         return out
 
     def set_device_coder(self, on=True):
@@ -649,6 +730,34 @@ class FFV2Encoder:
         return [(buf[n * per: n * per + yb].view(self.dtype).reshape(ys), buf[n * per + yb: n * per + yb + cb].view(self.dtype).reshape(cs))
                 for n in range(count)]
 
+    def ring_send_packed(self, src, fmt, tag=0, pinned=False, register=False):
+        """A packed RGB frame (H, W, C), any row stride, through the ring: it crosses PCIe as it is and is converted on
+        the frame's compute stream.  False when the ring is full."""
+        flags = FRAME_PACKED | self.packed_fmt(fmt) << 16
+        _, ptr, ls = self._packed_host(src, fmt, copy=False)
+        data = (C.c_void_p * 4)(ptr, None, None, None)
+        lss = (C.c_ssize_t * 4)(ls, 0, 0, 0)
+        r = self._lib.ffv2amd_ring_send(self._h, data, lss, None, int(tag), flags | (1 if pinned else 0) | (4 if register else 0))
+        if r == -11:
+            return False
+        _lib.check(r, "ring_send(packed)")
+        return True
+
+    def pinned_frames_packed(self, count, fmt):
+        """count page-locked packed RGB frames as a list of (H, W, C) arrays (rows 128-byte aligned), for
+        ring_send_packed(pinned=True).  Free with free_pinned()."""
+        h, w, c = self.packed_shape(fmt)
+        dt = self.packed_dtype(fmt)
+        pitch = (w * c * dt.itemsize + 127) // 128 * 128
+        per = pitch * h
+        ptr = self._lib.ffv2amd_host_alloc(count * per)
+        if not ptr:
+            raise MemoryError("ffv2amd_host_alloc(%d)" % (count * per))
+        self._pinned = getattr(self, "_pinned", []) + [ptr]
+        buf = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * per,))
+        return [buf[n * per: (n + 1) * per].reshape(h, pitch)[:, : w * c * dt.itemsize].view(dt).reshape(h, w, c)
+                for n in range(count)]
+
     def ring_receive(self, wait=True):
         """-> (tag, packet bytes) of the oldest frame in flight, or None (nothing in flight /
         wait=False and not finished yet).  A failed frame raises FFV2Error."""
@@ -667,18 +776,23 @@ class FFV2Encoder:
         cap = packet_cap or self.info.packet_cap_qp
         self._qpring_out = np.empty(int(cap) + 16, np.uint8)
 
-    def qpring_send(self, frame, tag=0, W=None, pinned=False, yuv420=False, register=False, yuv422=False, nv=None):
+    def qpring_send(self, frame, tag=0, W=None, pinned=False, yuv420=False, register=False, yuv422=False, nv=None,
+                    packed=None):
         """frame: (P,H,W) host array, or with yuv420=True / yuv422=True the (Y, U, V) arrays of a yuv420p* / yuv422p*
-        frame, or with nv="nv12" (any name of NV_FORMATS) the (Y, interleaved chroma) arrays of a semi-planar frame.
+        frame, or with nv="nv12" (any name of NV_FORMATS) the (Y, interleaved chroma) arrays of a semi-planar frame, or
+        with packed="rgb24" (any name of PACKED_FORMATS) a packed RGB (H, W, C) array.
         False: EAGAIN (receive packets first, then send the frame again)."""
         i = self.info
-        planes = list(frame) if yuv420 or yuv422 or nv else [frame[p] for p in range(i.planes)]
         data = (C.c_void_p * 4)()
         ls = (C.c_ssize_t * 4)()
-        for p, a in enumerate(planes):
-            assert a.dtype == self.dtype and a.strides[1] == self.dtype.itemsize, (a.dtype, a.strides)
-            data[p] = a.ctypes.data
-            ls[p] = a.strides[0]
+        if packed:
+            _, data[0], ls[0] = self._packed_host(frame, packed, copy=False)
+        else:
+            planes = list(frame) if yuv420 or yuv422 or nv else [frame[p] for p in range(i.planes)]
+            for p, a in enumerate(planes):
+                assert a.dtype == self.dtype and a.strides[1] == self.dtype.itemsize, (a.dtype, a.strides)
+                data[p] = a.ctypes.data
+                ls[p] = a.strides[0]
         wp = None
         if W is not None:
             W = np.ascontiguousarray(W, np.int32)
@@ -686,7 +800,8 @@ class FFV2Encoder:
             wp = W.ctypes.data_as(C.c_void_p)
         r = self._lib.ffv2amd_qpring_send(self._h, data, ls, wp, int(tag),
                                           (1 if pinned else 0) | (2 if yuv420 else 0) | (4 if register else 0) |
-                                          (8 if yuv422 else 0) | (self.nv_flags(nv) if nv else 0))
+                                          (8 if yuv422 else 0) | (self.nv_flags(nv) if nv else 0) |
+                                          (FRAME_PACKED | self.packed_fmt(packed) << 16 if packed else 0))
         if r == -11:
             return False
         _lib.check(r, "qpring_send")

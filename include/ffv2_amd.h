@@ -209,6 +209,62 @@ int  ffv2amd_encode_frame_nv(ffv2amd_encoder *enc, const uint8_t *const data[2],
 int  ffv2amd_qp_send_frame_nv(ffv2amd_encoder *enc, const uint8_t *const data[2], const ptrdiff_t linesize[2], unsigned flags,
                               int qp, int64_t tag);
 
+/* Packed RGB front end: sources whose pixels are one plane of interleaved components, as screen capture, image
+ * decoders and renderers hand them over.  The source format is one of the FFV2AMD_PIX_* values below (the
+ * AVPixelFormat values of the reference tree, libavutil/pixfmt.h); the encoder's format picks what is accepted:
+ *     gbrp encoder                 rgb24 bgr24 argb rgba abgr bgra 0rgb rgb0 0bgr bgr0 (8-bit samples)
+ *     gbrp10le / gbrp12le encoder  rgb48le/be bgr48le/be rgba64le/be bgra64le/be (16-bit samples)
+ * Every other combination (an 8-bit source into gbrp10le/12le, a 16-bit one into gbrp, any of them into yuv444p* or
+ * gray, an unknown format) is FFV2AMD_ERR_INVAL, returned before a device is touched.  What the reference tool chain
+ * does: av_find_best_pix_fmt_of_2 / get_pix_fmt_score (libavutil/pixdesc.c:2714-2873) over ffv2enc.c:596-601 pick
+ * gbrp for 8-bit and gbrp12le for 16-bit packed RGB, alpha dropped; libswscale's unscaled converters are exact:
+ * rgbToPlanarRgbWrapper / packedtogbr24p (libswscale/swscale_unscaled.c:1118-1190, dispatched at :2015-2017) permute
+ * the bytes, Rgb16ToPlanarRgb16Wrapper / packed16togbra16 (:540-732, dispatched at :1987-1999) byte-swap big-endian
+ * samples and shift right by 16 - depth (a gbrp10le encoder gets >> 6 from the same code).  The conversion is
+ * bit-exact to those lines.  DEVIATION: rgb0 / bgr0 / 0rgb / 0bgr fall into rgbToPlanarRgbWrapper's default: branch,
+ * which writes nothing -- there is no reference output; they are converted here as rgba / bgra / argb / abgr with
+ * the padding byte ignored.
+ *   frame_bytes_packed     : bytes of a tightly packed frame (h * w * bytes per pixel); 0 for a NULL encoder or a
+ *                            refused combination.
+ *   convert_packed_device  : nframes pitched device surfaces (frame f at d_src + f * frame_stride, rows src_pitch
+ *                            bytes apart, any alignment) -> the encoder's frame layout (d_frames444, ready for
+ *                            encode_batch_device / lanecoder_submit), on `stream`.  Only the picture's samples are
+ *                            written, never a row's padding.
+ *   encode_frame_packed    : one host frame (data rows `linesize` bytes apart) -> packet, any qp.
+ *   qp_send_frame_packed   : the same frame into the qp > 0 pipeline (see ffv2amd_qp_send_frame_420).
+ * ffv2amd_ring_send and ffv2amd_qpring_send take such frames with flags FFV2AMD_FRAME_PACKED |
+ * FFV2AMD_FRAME_SRC_FMT(fmt) (data[0] = the packed plane): the frame crosses PCIe as it is, into staging, and is
+ * converted on the frame's compute stream.  The source format field (bits 16-23) is read only when
+ * FFV2AMD_FRAME_PACKED is set; FFV2AMD_FRAME_PACKED with FFV2AMD_FRAME_NV, _NV_VU, _YUV420 or _YUV422 is
+ * FFV2AMD_ERR_INVAL. */
+#define FFV2AMD_PIX_RGB24       2
+#define FFV2AMD_PIX_BGR24       3
+#define FFV2AMD_PIX_ARGB       25
+#define FFV2AMD_PIX_RGBA       26
+#define FFV2AMD_PIX_ABGR       27
+#define FFV2AMD_PIX_BGRA       28
+#define FFV2AMD_PIX_RGB48BE    34
+#define FFV2AMD_PIX_RGB48LE    35
+#define FFV2AMD_PIX_BGR48BE    59
+#define FFV2AMD_PIX_BGR48LE    60
+#define FFV2AMD_PIX_RGBA64BE  106
+#define FFV2AMD_PIX_RGBA64LE  107
+#define FFV2AMD_PIX_BGRA64BE  108
+#define FFV2AMD_PIX_BGRA64LE  109
+#define FFV2AMD_PIX_0RGB      120
+#define FFV2AMD_PIX_RGB0      121
+#define FFV2AMD_PIX_0BGR      122
+#define FFV2AMD_PIX_BGR0      123
+#define FFV2AMD_FRAME_PACKED  64u
+#define FFV2AMD_FRAME_SRC_FMT(fmt) (((unsigned)(fmt) & 0xffu) << 16)
+size_t ffv2amd_frame_bytes_packed(const ffv2amd_encoder *enc, int src_fmt);
+int  ffv2amd_convert_packed_device(ffv2amd_encoder *enc, int nframes, const void *d_src, size_t src_pitch,
+                                   size_t frame_stride, int src_fmt, void *d_frames444, void *stream);
+int  ffv2amd_encode_frame_packed(ffv2amd_encoder *enc, const uint8_t *data, ptrdiff_t linesize, int src_fmt,
+                                 int qp, uint8_t *out, size_t out_cap, size_t *out_size);
+int  ffv2amd_qp_send_frame_packed(ffv2amd_encoder *enc, const uint8_t *data, ptrdiff_t linesize, int src_fmt,
+                                  int qp, int64_t tag);
+
 /* The same batch step for 1 <= qp <= 64 split in two, so that consecutive batches overlap:
  *   qp_submit : T-stage, PVQ search and symbol compaction of one batch, asynchronous on the
  *               encoder's stream (frames must be complete when it is called); at most two
@@ -259,7 +315,8 @@ int  ffv2amd_qp_pending(const ffv2amd_encoder *enc);
  *                    ordinary memory from a pool of long-lived buffers, page-locked here on first sight) and/or
  *                    FFV2AMD_FRAME_YUV420 (data = Y, U, V of a yuv420p* frame) or FFV2AMD_FRAME_YUV422 (of a
  *                    yuv422p* frame; both at once is FFV2AMD_ERR_INVAL), or FFV2AMD_FRAME_NV (data = Y, chroma of a
- *                    semi-planar frame, see ffv2amd_frame_bytes_nv) -- one batch may mix them all; otherwise the rows are copied before
+ *                    semi-planar frame, see ffv2amd_frame_bytes_nv), or FFV2AMD_FRAME_PACKED | FFV2AMD_FRAME_SRC_FMT(fmt)
+ *                    (data[0] = a packed RGB frame, see ffv2amd_frame_bytes_packed) -- one batch may mix them all; otherwise the rows are copied before
  *                    the call returns (into about 256 MB of page-locked bounce frames the ring owns, by helper
  *                    threads as in ring_send: FFV2AMD_GATHER_THREADS).
  *                    FFV2AMD_ERR_AGAIN: a batch is full, two calls are in flight and the packets of the one
@@ -352,6 +409,10 @@ int    ffv2amd_debug_upconv422_time(ffv2amd_encoder *enc, int nframes, const voi
 int    ffv2amd_debug_nv_time(ffv2amd_encoder *enc, int nframes, const void *d_y, size_t y_pitch, const void *d_uv,
                              size_t uv_pitch, size_t frame_stride, unsigned flags, void *d_frames444, int reps,
                              float *ms_per_launch);
+/* Benchmark aid: ffv2amd_convert_packed_device on the encoder's stream after one warm-up launch: average ms per launch
+ * over `reps` launches (tools/bench_packed.py). */
+int    ffv2amd_debug_packed_time(ffv2amd_encoder *enc, int nframes, const void *d_src, size_t src_pitch,
+                                 size_t frame_stride, int src_fmt, void *d_frames444, int reps, float *ms_per_launch);
 int    ffv2amd_lanecoder_encode(ffv2amd_encoder *enc, int nframes, const void *d_frames, int qp,
                                 const int32_t *d_W, uint8_t *h_packets, size_t packet_stride,
                                 uint32_t *h_sizes, int32_t *h_status);
@@ -413,6 +474,8 @@ int  ffv2amd_encoder_flush(ffv2amd_encoder *enc, void *stream);
  *   ring_send    : FFV2AMD_ERR_AGAIN when `depth` frames are in flight (receive one first).
  *                  flags & FFV2AMD_FRAME_NV: data[0] = Y, data[1] = interleaved chroma of a semi-planar frame
  *                  (see ffv2amd_frame_bytes_nv), converted on the device in front of the T-stage.
+ *                  flags & FFV2AMD_FRAME_PACKED: data[0] = a packed RGB frame of the format
+ *                  FFV2AMD_FRAME_SRC_FMT(fmt) carries (see ffv2amd_frame_bytes_packed), converted likewise.
  *                  flags & FFV2AMD_FRAME_PINNED: the planes are page-locked (ffv2amd_host_alloc,
  *                  hipHostMalloc/hipHostRegister) and stay untouched until the frame's packet has
  *                  been received -- the DMA engine then reads them in place (planes that follow

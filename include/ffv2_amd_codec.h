@@ -79,7 +79,8 @@ int  ffv2amd_codec_close(FFV2AMDCodecContext *avctx);            /* ffv2enc.c:51
  * finishes first.  flags: FFV2AMD_FRAME_PINNED, FFV2AMD_FRAME_REGISTER, FFV2AMD_FRAME_YUV420 or FFV2AMD_FRAME_YUV422 of
  * ffv2_amd.h (frame->data[0..2] = Y, U, V of a yuv420p* / yuv422p* frame of the context's depth, see
  * ffv2amd_codec_encode_yuv420 / _yuv422; both at once is FFV2AMD_ERR_INVAL), or FFV2AMD_FRAME_NV with FFV2AMD_FRAME_NV_VU
- * and the subsampling flags (frame->data[0..1] = Y, interleaved chroma of a semi-planar frame, see ffv2amd_codec_encode_nv).
+ * and the subsampling flags (frame->data[0..1] = Y, interleaved chroma of a semi-planar frame, see ffv2amd_codec_encode_nv),
+ * or FFV2AMD_FRAME_PACKED | FFV2AMD_FRAME_SRC_FMT(fmt) (frame->data[0] = a packed RGB frame, see ffv2amd_codec_encode_packed).
  * global_quality 1..64 goes through ffv2amd_qp_send_frame / _receive_packet: two frames in flight per
  * device, receive_packet always waits (it runs the frame's range coder), a frame the reference
  * would abort on comes back as FFV2AMD_ERR_ABORT.  global_quality must not change while frames
@@ -100,6 +101,11 @@ int  ffv2amd_codec_encode_yuv422(FFV2AMDCodecContext *avctx, FFV2AMDPacket *avpk
  * ffv2_amd.h (ffv2amd_frame_bytes_nv).  Parity unpinned. */
 int  ffv2amd_codec_encode_nv(FFV2AMDCodecContext *avctx, FFV2AMDPacket *avpkt,
                              const FFV2AMDFrame *frame, unsigned flags, int *got_packet_ptr);
+/* ... and for packed RGB sources: frame->data[0] = the packed plane, src_fmt one of the FFV2AMD_PIX_* source formats
+ * of ffv2_amd.h (8-bit ones for a gbrp context, 16-bit ones for gbrp10le / gbrp12le; ffv2amd_frame_bytes_packed).
+ * The conversion is exact (libswscale's unscaled converters); rgb0 / bgr0 / 0rgb / 0bgr deviate deliberately. */
+int  ffv2amd_codec_encode_packed(FFV2AMDCodecContext *avctx, FFV2AMDPacket *avpkt,
+                                 const FFV2AMDFrame *frame, int src_fmt, int *got_packet_ptr);
 void ffv2amd_packet_unref(FFV2AMDPacket *pkt);
 
 #ifdef __cplusplus
